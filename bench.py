@@ -14,11 +14,23 @@ pictures complete inside it (checked: `pictures_completed`), so the value does n
 --steps (h264-jm-commentary_amd/streams.py).  Entropy coding is excluded, as in JM's ME/transform
 time (BASELINE.md).
 
-Also reported (never `value`): the PCIe-inclusive rate of the host-buffer path (jmh_frame_push /
+A plain run sets up, warms up, times the steps and prints the line.  --full also reports (never
+`value`): the PCIe-inclusive rate of the host-buffer path (jmh_frame_push /
 jmh_frame_pop: source H2D, results + reconstruction D2H; SURVEY §8d's submit-to-host-visible
-timer), the single-picture latency (push -> results host-visible on an empty pipeline), and a
-correctness check — the CPU baseline's I + P pictures encoded on the GPU and compared with the
-oracle's results of the same run (`verified`).
+timer), the single-picture latency (push -> results host-visible on an empty pipeline), the CPU
+baseline, and a correctness check — the CPU baseline's I + P pictures encoded on the GPU and
+compared with the oracle's results of the same run (`verified`).  Without --full these fields of
+the line are null.
+
+--dump-outputs DIR writes, after the timed steps, what the timed chain hands on as DIR/<name>.npy
+(float32; the 32-bit result fields float64).  The timed path keeps every picture in HBM and returns
+nothing to the host, so the arrays are those of the chain's next picture, encoded against the last
+timed step's output (its deblocked picture, the reference) through the read-back entry point: the
+macroblock results field by field (res_*), the reconstruction (rec_y/u/v) and the deblocked
+picture (dbk_y/u/v).  They depend on every sample the last timed step produced.  The source
+pictures are a function of the arguments alone (seed = rank), so two builds run with the same
+arguments can be compared array for array.  Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of
+every array is kept.
 
 Multi-GPU (config 4): one independent stream per rank (seed = rank), no collective in the data
 path; a gloo barrier brackets the timed region and the maximum time over ranks is used.
@@ -310,6 +322,57 @@ def read_pmc_traffic(config, search_mode, t8=None, slice_mbs=None):
 
 
 # ------------------------------------------------------------------------------------------
+# --dump-outputs: the arrays the timed chain hands on
+# ------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 60 * 10 ** 6      # all files of one dump together (kept below 64 MB)
+
+
+def dump_arrays(res, rec, dbk):
+    """{name: float array} of one read-back picture: every field of the macroblock results (32-bit
+    fields as float64, the rest float32), the reconstruction and, where deblocked, that picture."""
+    import numpy as np
+    out = {}
+    for name in res.dtype.names:
+        if name in ("pad0", "reserved"):
+            continue
+        a = res[name]
+        out["res_" + name] = a.astype(np.float64 if a.dtype.itemsize > 2 else np.float32).reshape(len(res), -1)
+    for tag, planes in (("rec", rec), ("dbk", dbk)):
+        if planes is not None:
+            for k, p in zip("yuv", planes):
+                out[f"{tag}_{k}"] = p.astype(np.float32)
+    return out
+
+
+def sample_arrays(arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays as they are when they fit in `limit` bytes together; else the same fraction of every
+    array's elements (flattened, in order), picked by a generator with a fixed seed."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total <= limit:
+        return arrays
+    rng = np.random.default_rng(0)
+    out = {}
+    for name in sorted(arrays):
+        a = arrays[name].reshape(-1)
+        keep = max(1, int(a.size * limit / total))
+        out[name] = a[np.sort(rng.choice(a.size, keep, replace=False))]
+    return out
+
+
+def dump_outputs(jm, enc, stream, frames, step, out_dir, prefix=""):
+    """Encode step number `step` of the stream's chain (the one after the timed steps) with
+    read-back and write its arrays to out_dir/<prefix><name>.npy."""
+    import numpy as np
+    enc.set_reference_slot(stream.ref_slot)
+    res, rec = enc.encode(*frames[1 + step % stream.nseq], jm.JMH_P_SLICE, QP, deblock=stream.deblock)
+    dbk = None if stream.deblock is None else enc.deblocked()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in sample_arrays(dump_arrays(res, rec, dbk)).items():
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+
+
+# ------------------------------------------------------------------------------------------
 # the host-buffer path: PCIe-inclusive rate and single-picture latency (reported, not `value`)
 # ------------------------------------------------------------------------------------------
 def pcie_inclusive(jm, enc, frames, pictures):
@@ -393,8 +456,13 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--frames", type=int, default=60, help="P pictures of the resident source sequence")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive / latency measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline with the oracle "
+                         "comparison (`verified`) and the PCIe-inclusive host path with the single-picture latency")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the timed chain hands on as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline / oracle comparison")
+    ap.add_argument("--no-host-path", action="store_true", help="--full without the PCIe-inclusive / latency measurement")
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 5),
                     help="BASELINE.json config: 2 = 1080p Baseline FFS (the headline), 3 = 2160p High EPZS + 8x8, "
                          "5 = 2160p High 10 EPZS, CABAC RDO on, 240-MB slices")
@@ -465,8 +533,11 @@ def main():
     dt = streams.timed_run(stream, args.steps, args.warmup, dist, on_start=enc.timing)   # on_start resets the event sums
     tm = enc.timing()                                     # event sums of the timed steps only
 
+    if args.dump_outputs:
+        dump_outputs(jm, enc, stream, frames, stream.warmup_steps + args.steps, args.dump_outputs,
+                     f"rank{rank}_" if world > 1 else "")
     host = None
-    if not args.no_host_path and size is None and not args.no_deblock:
+    if args.full and not args.no_host_path and size is None and not args.no_deblock:
         host = pcie_inclusive(jm, enc, frames, max(120, 3 * enc.depth))
     if args.dump:                                         # test: one read-back picture after the chain
         import numpy as np
@@ -577,6 +648,7 @@ def main():
         "vs_baseline": None,
         "dtype": "u16" if BD > 8 else "u8",
         "data": "synthetic",
+        "full": args.full,
         "config": {
             "workload": cfg["workload"].replace("{sm}", sm_name).replace("{nf}", str(args.frames))
                         + (f", SliceMode=1 SliceArgument={SLICE_MBS} ({-(-NMB // SLICE_MBS)} slices per picture)"
@@ -620,7 +692,7 @@ def main():
         "verified": None,                                 # the oracle comparison (cpu_baseline leg)
         "cpu_baseline": None,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         with tempfile.TemporaryDirectory() as tmp:
             out["cpu_baseline"] = cpu_baseline(args.config, search_mode, tmp, cfg["t8"])
             out["verified"] = verify_against_oracle(jm, os.path.join(tmp, "oracle_seed0.npz"), search_mode, cfg["t8"],

@@ -67,6 +67,35 @@ def test_exit_status():
     assert b.exit_status(False, False)[0] == 3
 
 
+def test_dump_arrays_and_sample():
+    """--dump-outputs: every result field and plane becomes a float array that holds its integers
+    exactly (32-bit fields float64), and a dump beyond the byte limit keeps the same seeded sample
+    of every array on every call"""
+    import numpy as np
+    from jmpaths import load_jmhip
+    b = load_bench()
+    jm = load_jmhip()
+    rng = np.random.default_rng(1)
+    res = np.frombuffer(rng.integers(0, 256, 6 * jm.MB_RESULT_DTYPE.itemsize, dtype=np.uint8).tobytes(),
+                        dtype=jm.MB_RESULT_DTYPE)
+    rec = tuple(rng.integers(0, 1024, s, dtype=np.uint16) for s in ((32, 48), (16, 24), (16, 24)))
+    arrays = b.dump_arrays(res, rec, None)
+    assert set(arrays) == {"res_" + n for n in res.dtype.names if n not in ("pad0", "reserved")} | {"rec_y", "rec_u", "rec_v"}
+    for name, a in arrays.items():
+        src = res[name[4:]].reshape(len(res), -1) if name.startswith("res_") else rec["yuv".index(name[-1])]
+        assert a.dtype == (np.float64 if src.dtype.itemsize > 2 else np.float32)
+        assert np.array_equal(a.astype(src.dtype), src)
+    assert set(b.dump_arrays(res, rec, rec)) == set(arrays) | {"dbk_y", "dbk_u", "dbk_v"}
+    assert b.sample_arrays(arrays) is arrays and b.DUMP_LIMIT_BYTES <= 64 * 10 ** 6
+    total = sum(a.nbytes for a in arrays.values())
+    small = b.sample_arrays(arrays, total // 3)
+    again = b.sample_arrays(arrays, total // 3)
+    assert set(small) == set(arrays) and sum(a.nbytes for a in small.values()) <= total // 3
+    for name, a in small.items():
+        assert a.dtype == arrays[name].dtype and 1 <= a.size < arrays[name].size
+        assert np.array_equal(a, again[name]) and np.isin(a, arrays[name]).all()
+
+
 def test_metric_names_timer():
     """every bench metric says which timer `value` uses (device-resident; the PCIe-inclusive rate
     is host_path.pcie_inclusive_mp_s)"""

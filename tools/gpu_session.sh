@@ -9,14 +9,14 @@
 #   fast    pytest -m "gpu and not slow"             -> gpurun_out/TAG_pytest.log
 #   rdo     pytest tests/test_rdo_gpu.py (RDOptimization 1; failures reported, not fatal)
 #   smoke   __graft_entry__.smoke()                  -> gpurun_out/TAG_smoke.log
-#   bench   bench.py (defaults, with CPU baseline)   -> gpurun_out/TAG_bench.json
+#   bench   bench.py --full (defaults, with CPU baseline and host path) -> $OUT/TAG_bench.json
 #   bench20 bench.py --steps 20 --warmup 5 (the driver's invocation, no CPU baseline)
 #   benchf8 bench20 with JMH_FINAL_OCC8=1 (k_mb_final's 8-per-CU build for every tick: A/B)
-#   c3      bench.py --config 3 (with CPU baseline)  -> gpurun_out/TAG_c3_bench.json
+#   c3      bench.py --config 3 --full (with CPU baseline) -> $OUT/TAG_c3_bench.json
 #   c3s     config 3 with SliceMode 1, SliceArgument 240 (config 5's one-row slices, 8-bit, CAVLC)
-#   c5      bench.py --config 5 (High 10, RDO on, 240-MB slices; with CPU baseline)
+#   c5      bench.py --config 5 --full (High 10, RDO on, 240-MB slices; with CPU baseline)
 #   c5q     the same, 60 steps, no CPU baseline / host path (a quick GPU number)
-#   c5off   config 5's RDO-off variant (EPZS + 8x8 transform)
+#   c5off   config 5's RDO-off variant (EPZS + 8x8 transform), --full without the CPU baseline
 #   c5t8    config 5 with Transform8x8Mode 1 (RDO on: 8x8-transform candidates, I8MB; with CPU baseline)
 #   lencodc5 lencodc3 with one slice and with SliceArgument 240 (135 one-row slices per picture)
 #   prof    rocprofv3 --kernel-trace --stats of the bench -> gpurun_out/prof_TAG/
@@ -30,6 +30,8 @@ TAG=${1:?tag}; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R" || exit 1
 mkdir -p gpurun_out
+OUT=${JMH_SESSION_OUT:-session_out}   # where the --full bench steps write their lines
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() {   # name limit cmd...
     local name=$1 lim=$2; shift 2
@@ -57,26 +59,26 @@ for s in "$@"; do
             [ $rc -eq 0 ] || exit $rc ;;
     smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1 || exit $?
             cat gpurun_out/${TAG}_smoke.log ;;
-    bench)  run bench 600 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit $?
-            cat gpurun_out/${TAG}_bench.json ;;
+    bench)  run bench 600 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit $?
+            cat $OUT/${TAG}_bench.json ;;
     bench20) run bench20 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_bench20.json || exit $?
             cat gpurun_out/${TAG}_bench20.json ;;
     benchf8) JMH_FINAL_OCC8=1 run benchf8 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_benchf8.json || exit $?
             cat gpurun_out/${TAG}_benchf8.json ;;
-    c3)     run c3 900 python bench.py --config 3 > gpurun_out/${TAG}_c3_bench.json 2> gpurun_out/${TAG}_c3_bench.err || exit $?
-            cat gpurun_out/${TAG}_c3_bench.json ;;
-    c5)     run c5 1100 python bench.py --config 5 > gpurun_out/${TAG}_c5_bench.json 2> gpurun_out/${TAG}_c5_bench.err || exit $?
-            cat gpurun_out/${TAG}_c5_bench.json ;;
-    c5t8)   run c5t8 1100 python bench.py --config 5 --t8 1 > gpurun_out/${TAG}_c5t8_bench.json 2> gpurun_out/${TAG}_c5t8_bench.err || exit $?
-            cat gpurun_out/${TAG}_c5t8_bench.json ;;
+    c3)     run c3 900 python bench.py --full --config 3 > $OUT/${TAG}_c3_bench.json 2> $OUT/${TAG}_c3_bench.err || exit $?
+            cat $OUT/${TAG}_c3_bench.json ;;
+    c5)     run c5 1100 python bench.py --full --config 5 > $OUT/${TAG}_c5_bench.json 2> $OUT/${TAG}_c5_bench.err || exit $?
+            cat $OUT/${TAG}_c5_bench.json ;;
+    c5t8)   run c5t8 1100 python bench.py --full --config 5 --t8 1 > $OUT/${TAG}_c5t8_bench.json 2> $OUT/${TAG}_c5t8_bench.err || exit $?
+            cat $OUT/${TAG}_c5t8_bench.json ;;
     c5q)    run c5q 600 python bench.py --config 5 --steps 60 --no-cpu-baseline --no-host-path > gpurun_out/${TAG}_c5q_bench.json \
                 2> gpurun_out/${TAG}_c5q_bench.err || exit $?
             cat gpurun_out/${TAG}_c5q_bench.json ;;
-    c5off)  run c5off 900 python bench.py --config 5 --rdo 0 --no-cpu-baseline > gpurun_out/${TAG}_c5off_bench.json \
-                2> gpurun_out/${TAG}_c5off_bench.err || exit $?
-            cat gpurun_out/${TAG}_c5off_bench.json ;;
-    c3s)    run c3s 900 python bench.py --config 3 --slice-mbs 240 > gpurun_out/${TAG}_c3s_bench.json 2> gpurun_out/${TAG}_c3s_bench.err || exit $?
-            cat gpurun_out/${TAG}_c3s_bench.json ;;
+    c5off)  run c5off 900 python bench.py --full --config 5 --rdo 0 --no-cpu-baseline > $OUT/${TAG}_c5off_bench.json \
+                2> $OUT/${TAG}_c5off_bench.err || exit $?
+            cat $OUT/${TAG}_c5off_bench.json ;;
+    c3s)    run c3s 900 python bench.py --full --config 3 --slice-mbs 240 > $OUT/${TAG}_c3s_bench.json 2> $OUT/${TAG}_c3s_bench.err || exit $?
+            cat $OUT/${TAG}_c3s_bench.json ;;
     prof)   run prof 600 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/prof_${TAG}" -o ${TAG} --output-format csv -- \
                 python3 "$R/bench.py" --no-cpu-baseline --no-host-path > gpurun_out/${TAG}_prof.log 2>&1 || exit $?
             find gpurun_out/prof_${TAG} -name "*kernel_stats*" -exec cat {} \; ;;
