@@ -36,9 +36,7 @@
 //   * sub-pel on one wave per search: a quad of lanes per candidate, DPP butterflies / packed
 //     int16 Hadamard, one wave minimum per half / quarter pass.
 #include "jmh_common.h"
-#ifndef JMH_EXP
-#define JMH_EXP 0                             // tools/valu_split.sh builds variants without parts
-#endif
+#include "jmh_launch.h"
 #include "jmh_intra8.h"
 #include "jmh_intra.h"
 #include "jmh_i4.h"
@@ -57,18 +55,18 @@ struct MeS {
     IntraNb<uint8_t> nb;
     int16_t all_mv[8][16][2];
     int motion_cost[8][4];
-    unsigned red[NTS / 64][MAXNS];            // per search wave, per search of the stage: argmin keys
+    unsigned red[NTA / 64][MAXNS];            // per search wave, per search of the stage: argmin keys
     int pmv[MAXNS][2];                        // MVPs of the next stage's searches (forwarded)
     uint16_t mvc[MVB_LEN];                    // lambda * mvbits(v) at [v + MVB_OFF] (|v| <= 4*2*SR + 259)
     uint8_t planes[4 * PLS];                  // G (the window), b, h, j
     union {
         int16_t h1[WIN_DIM_MAX * WST];        // unclipped vertical 6-tap intermediates (planes only)
-        uint2 sad8[NPK * NTS];                // then: the 8x8 SADs of every thread's positions,
+        uint2 sad8[NPK * NTA];                // then: the 8x8 SADs of every thread's positions,
     } hs;                                     //   [k][thread] (16x16 / 16x8 / 8x16 searches)
     unsigned long long *pst;                  // debug: per-stage stamps (thread 0), null when off
     int pn;
-    unsigned bar;                             // JMH_I4WAVE: arrivals at the search waves' barriers (search_sync)
-    IntraS<uint8_t> in;                       // the MB's intra decisions, run by waves 6 and 7
+    alignas(8) IntraS<uint8_t> in;            // the MB's intra decisions, run by waves 6 and 7 (8-aligned: its
+                                              //   members' 64-bit LDS accesses stay aligned)
 };
 union AnalyseS {
     MeS me;
@@ -123,7 +121,6 @@ struct PosState {
                              // pre-check, else spiral index + 1; 0xFFFF for slots outside the table
     int dx, dy0;
     int scx, scy;            // window centre (full pel, relative to the MB)
-    unsigned bgen;           // JMH_I4WAVE: arrivals search_sync waits for (wave-uniform)
 };
 
 // optimisation fence on the register-resident search state, once per stage: keeps the compiler
@@ -206,9 +203,6 @@ __device__ __forceinline__ uint32_t pack4(s16x2 lo, s16x2 hi) { return __builtin
 // HALF: a half-pel (or full-pel) position, whose sample is one plane's (A == B): B is not read
 template <bool HALF>
 __device__ __forceinline__ int subblock_satd(const MeS &s, int wbase, int obase, int ox, int oy, int had) {
-#if JMH_EXP & 1   // instruction-count experiment (tools/valu_split.sh): no sub-pel SATD
-    return 0;
-#endif
     const int off = qoff((oy & 3) * 4 + (ox & 3));
     const int xa = (off >> 12) & 15, ya = (off >> 8) & 15, xb = (off >> 4) & 15, yb = off & 15;
     const int oA = ((xa & 1) + 2 * (ya & 1)) * PLS + (ya >> 1) * WST + (xa >> 1);
@@ -263,9 +257,6 @@ __device__ __forceinline__ int subblock_satd(const MeS &s, int wbase, int obase,
 // quad by DPP, the result is this row's share (the quad sum is the block's SATD)
 template <bool HALF>
 __device__ __forceinline__ int quad_row_satd(const MeS &s, int wbase, int obase, int ox, int oy, int row, int had) {
-#if JMH_EXP & 1
-    return 0;
-#endif
     const int off = qoff((oy & 3) * 4 + (ox & 3));
     const int xa = (off >> 12) & 15, ya = (off >> 8) & 15, xb = (off >> 4) & 15, yb = off & 15;
     const int oA = ((xa & 1) + 2 * (ya & 1)) * PLS + (ya >> 1) * WST + (xa >> 1);
@@ -308,7 +299,7 @@ __device__ __forceinline__ void subpel_wave(const DevParams &d, MeS &s, int j, c
     const int sr = d.sr, lam = d.lambda_motion, had = d.use_hadamard;
     unsigned best = s.red[0][j];
 #pragma unroll
-    for (int w = 1; w < NTS / 64; w++) best = min(best, s.red[w][j]);
+    for (int w = 1; w < NTA / 64; w++) best = min(best, s.red[w][j]);
     const unsigned order = best & 8191u;
     int rx, ry;
     if (order == 0) { rx = -scx; ry = -scy; }
@@ -401,28 +392,7 @@ __device__ __forceinline__ void subpel_wave(const DevParams &d, MeS &s, int j, c
 // the wave of a stage's search j: waves 0, 1, 4, 5 (SIMDs 0 and 1) first, so that the Intra4x4
 // waves 6 and 7 (SIMDs 2 and 3) share their SIMDs with no sub-pel wave of the workgroup in stages
 // of up to four searches
-#ifndef JMH_SWMAP
-#define JMH_SWMAP 1
-#endif
-__device__ __forceinline__ constexpr int search_wave(int j) { return JMH_SWMAP ? (0x6325410 >> (4 * j)) & 15 : j; }
-
-// barrier of the search waves.  JMH_I4WAVE: the seven search waves count their arrivals in LDS
-// (one monotonic counter, the release / acquire fences order the stage's LDS writes and reads
-// around it) -- an s_barrier would also wait for the intra wave 7, which runs its own chain.  Every
-// search wave reaches every barrier, so the poll always ends.
-__device__ __forceinline__ void search_sync(MeS &s, PosState &ps) {
-#if JMH_I4WAVE
-    ps.bgen += NTS / 64;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (__lane_id() == 0) __hip_atomic_fetch_add(&s.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&s.bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < ps.bgen)
-        __builtin_amdgcn_s_sleep(1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#else
-    (void)s; (void)ps;
-    __syncthreads();
-#endif
-}
+__device__ __forceinline__ constexpr int search_wave(int j) { return (0x6325410 >> (4 * j)) & 15; }
 
 template <int NS, bool FWD, class EV, class IDLE>
 __device__ __forceinline__ void me_stage(const DevParams &d, MeS &s, PosState &ps, const SDesc (&sd)[NS], int b8, int best8x8, EV ev,
@@ -446,7 +416,7 @@ __device__ __forceinline__ void me_stage(const DevParams &d, MeS &s, PosState &p
                 set_mvp(NbMe{s, sd[j].bt, b8, best8x8}, sd[j].bx4, sd[j].by4, 4 << lw4_of(sd[j].bt), 4 << lh4_of(sd[j].bt), mx, my);
                 if (lane == 0) { s.pmv[j][0] = mx; s.pmv[j][1] = my; }
             }
-        search_sync(s, ps);
+        __syncthreads();
 #pragma unroll
         for (int j = 0; j < NS; j++) {   // uniform: SGPRs
             pmx[j] = __builtin_amdgcn_readfirstlane(s.pmv[j][0]);
@@ -459,21 +429,17 @@ __device__ __forceinline__ void me_stage(const DevParams &d, MeS &s, PosState &p
         const unsigned v = wave_min_u32(bk[j]);
         if (lane == 0) s.red[wave][j] = v;
     }
-    search_sync(s, ps);
+    __syncthreads();
     sstamp(s, wave);
 #pragma unroll
     for (int j = 0; j < NS; j++)
         if (wave == search_wave(j)) subpel_wave(d, s, j, sd[j], pmx[j], pmy[j], ps.scx, ps.scy, b8, best8x8);
-#if !JMH_I4WAVE
     if constexpr (NS <= 6) {
         if (islot >= 0 && wave >= 6) idle(islot, wave - 6);   // the MB's Intra4x4 on otherwise idle waves
     } else {
         if (islot >= 0 && wave == 7) idle(islot, 0);          // one free wave: a one-block step
     }
-#else
-    (void)islot; (void)idle;
-#endif
-    search_sync(s, ps);
+    __syncthreads();
     sstamp(s, wave);
 }
 
@@ -499,7 +465,7 @@ __device__ __forceinline__ void eval_sad8(const MeS &s, const PosState &ps, int 
         const int rx = abs(ps.dx - sr);
 #pragma unroll
         for (int k = 0; k < NPK; k++) {
-            const uint2 v = s.hs.sad8[k * NTS + tid];
+            const uint2 v = s.hs.sad8[k * NTA + tid];
             const uint32_t r[2] = {v.x, v.y};
             const uint32_t o = ordk_of(ps, k);
             unsigned c[3];
@@ -526,9 +492,6 @@ __device__ __forceinline__ void eval_sad8(const MeS &s, const PosState &ps, int 
 // column at a time keeps the unrolled window rows (3 dwords each) within the register budget.
 template <bool EIGHT, int OX, int OY, int SLOT, int HI>
 __device__ __forceinline__ void sad_strip(const MeS &s, PosState &ps) {
-#if JMH_EXP & 4   // instruction-count experiment: no SAD strips
-    return;
-#endif
     const int wx = ps.dx + WM + OX;
     const uint32_t sel = wx & 3;
     const uint8_t *wb = s.planes + (ps.dy0 + WM + OY) * WST + (wx & ~3);
@@ -583,7 +546,7 @@ __device__ __forceinline__ void p8x8_block(const DevParams &d, MeS &s, PosState 
 #pragma unroll
     for (int k = 0; k < NPK; k++) {
         const uint32_t a = ps.sadp[k][0], b = ps.sadp[k][1];
-        reinterpret_cast<uint16_t *>(&s.hs.sad8[k * NTS + tid])[B8] = (uint16_t)((a & 0xFFFFu) + (a >> 16) + (b & 0xFFFFu) + (b >> 16));
+        reinterpret_cast<uint16_t *>(&s.hs.sad8[k * NTA + tid])[B8] = (uint16_t)((a & 0xFFFFu) + (a >> 16) + (b & 0xFFFFu) + (b >> 16));
     }
     if constexpr (B8 == 3) {
         // stage 0: 8x8, 8x4 upper, 4x8 left, 4x4 top-left + 16x16, 16x8 upper, 8x16 left
@@ -702,7 +665,6 @@ __device__ __forceinline__ void chroma_decision(const DevParams &d, const IntraN
 //  motion search of one P macroblock (all 41 searches)
 // ======================================================================================
 __device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &s, MbScratch *scr, int k, int w, int mbx, int mby);
-__device__ __forceinline__ void intra_wave(const DevParams &d, IntraS<uint8_t> &s, MbScratch *scr, int mbx, int mby);
 
 // the part of me_mb's setup that reads no other workgroup's output (the source block, the lambda *
 // mvbits table, zeroed accumulators): k_mb_flow runs it while its dependencies finish (pre = true
@@ -723,22 +685,14 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, int mbx, int m
     const bool prof = prof_mb_here(d, mbx, mby);
     PSTAMP(0);
     MbScratch *scr = d.scr + mby * d.mbw + mbx;
-    if (tid == 0) { s.pst = prof ? d.prof + 20 : nullptr; s.pn = 0; s.bar = 0; }
+    if (tid == 0) { s.pst = prof ? d.prof + 20 : nullptr; s.pn = 0; }
     if (tid < 256) { if (!pre) s.in.org[tid] = s.org[tid] = d.orgY[(pix_y + (tid >> 4)) * W + pix_x + (tid & 15)]; }
-#if JMH_I4WAVE
-    else if (tid < 384) load_orgc(d, s.in.nb, tid - 256, mbx, mby);   // the intra wave's chroma decision
-#endif
     else if (tid >= 384 && tid < 394) { load_border(d, s.bd, tid - 384, mbx, mby); load_border(d, s.in.bd, tid - 384, mbx, mby); }
     else if (!pre && tid >= 472 && tid < 478) s.in.part[(tid - 472) / 3][(tid - 472) % 3] = 0;
     else if (!pre && tid >= 480 && tid < 512) s.motion_cost[(tid - 480) >> 2][tid & 3] = 0;
     // the MB's Intra4x4 decision (10 diagonal steps, then the results) runs on waves 6 and 7
     // while the motion search's sub-pel waves work: slots 0..10 (intra_slot)
-#if JMH_EXP & 2   // instruction-count experiment: no Intra4x4 in the search workgroup
-    auto idle = [&](int, int) {};
-#else
     auto idle = [&](int k, int w) { intra_slot(d, s.in, scr, k, w, mbx, mby); };
-#endif
-    (void)scr;
     if (!pre)
         for (int i = tid; i < MVB_LEN; i += NTA) s.mvc[i] = (uint16_t)__umul24(d.lambda_motion, mvbits(i - MVB_OFF));
     int pcx = 0, pcy = 0, scx = 0, scy = 0;
@@ -796,7 +750,6 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, int mbx, int m
         ps.dx = sact ? tid % side : 0;
         ps.dy0 = sact ? (tid / side) * NPK : 0;
         ps.scx = scx; ps.scy = scy;
-        ps.bgen = 0;
         // (the 8x8 SADs of the 16x16 / 16x8 / 8x16 searches come from each 8x8 block's 4x4 SADs,
         // p8x8_block)
         PSTAMP(8);
@@ -874,14 +827,6 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, int mbx, int m
         }
         __syncthreads();   // h1 is dead: its LDS holds the 8x8 SADs from here on
         PSTAMP(2);
-#if JMH_I4WAVE
-        if (wave == NTS / 64) {   // the last s_barrier this wave meets: the intra decisions from here on
-#if !(JMH_EXP & 2)
-            intra_wave(d, s.in, scr, mbx, mby);
-#endif
-            return;
-        }
-#endif
         {   // ---- P8x8 (4 x 4 stages), the 16x16 / 16x8 / 8x16 searches inside block 3's stages 0, 1
             int best8x8 = 0, cost8x8 = 0;
             p8x8_block<0>(d, s, ps, best8x8, cost8x8, idle, wave, tid);
@@ -998,37 +943,6 @@ __device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &
     }
 }
 
-// JMH_I4WAVE: the intra decisions of a P macroblock on wave 7 of its motion-search workgroup, on
-// a schedule of their own (the search waves synchronise among themselves, search_sync): Intra4x4
-// over the 16 blocks in JM's decoding order on one wave (each block's neighbours are earlier in
-// it; the LDS writes of one wave are seen by its later reads), then the Intra16x16 and chroma
-// intra-mode decisions, so that no intra workgroup runs for a P picture's MBs
-__device__ __forceinline__ void intra_wave(const DevParams &d, IntraS<uint8_t> &s, MbScratch *scr, int mbx, int mby) {
-    const int lane = __lane_id();
-    const bool prof = prof_mb_here(d, mbx, mby, NTS / 64);   // debug (JMH_PHASE_PROF): stamps 60..62
-    PSTAMP(60);
-    const MbAvail mav = intra_avail(d, mbx, mby);
-    const int qpk = q_round(d.qsel, 15 + d.qp / 6);
-    int tabr[2];
-    i4_tabrow(lane, tabr);
-    int acc[3] = {0, 0, 0};                   // cost, cbp (per b8), block mask
-    for (int blk = 0; blk < 16; blk++) {
-        const int bx4 = 2 * ((blk >> 2) & 1) + (blk & 1), by4 = 2 * (blk >> 3) + ((blk >> 1) & 1);
-        i4_block(d, s, scr, 0, bx4, by4, tabr, mav.L, mav.T, mav.TL, mav.TR, qpk, acc);
-    }
-    if (lane == 0) {
-        scr->i4cost = 24 * d.lambda_mode + acc[0];   // 4 x (int)floor(6*lambda+0.4999)
-        scr->i4cbp = acc[1];
-        scr->i4blk = acc[2];
-    }
-    if (lane < 16) scr->ipred[lane] = s.ipred_cur[lane];
-    reinterpret_cast<uint32_t *>(scr->i4rec)[lane] = reinterpret_cast<const uint32_t *>(s.rec)[lane];
-    PSTAMP(61);
-    i16_decision(d, s.org, s.nb, scr, lane, mav.L, mav.T, mav.TL);
-    chroma_decision(d, s.nb, scr, lane, mav.L, mav.T, mav.TL);
-    PSTAMP(62);
-}
-
 #ifndef JMH_FLOW_TU   // the tick kernels (jmh_flow.hip builds k_mb_flow from the same device functions)
 __global__ __launch_bounds__(NTA, 4) void k_mb_analyse(const TickArgs t) {
     __shared__ AnalyseS s;
@@ -1050,7 +964,7 @@ __global__ __launch_bounds__(NTA, 4) void k_mb_analyse(const TickArgs t) {
         tag = 2u | (unsigned long long)(mby * d.mbw + mbx) << 4 | (unsigned long long)e << 32;
         me_mb(d, s.me, mbx, mby);
     } else {
-        const int q = __builtin_amdgcn_readfirstlane((JMH_I4WAVE ? nPm : 0) + 4 * (b - nPg) + (int)(threadIdx.x >> 7));
+        const int q = __builtin_amdgcn_readfirstlane(4 * (b - nPg) + (int)(threadIdx.x >> 7));
         const bool act = q < tot;
         const int e = tick_entry(t, act ? q : 0);
         const DevParams d = tick_params(t, e);
@@ -1073,9 +987,7 @@ __global__ __launch_bounds__(NTA, 4) void k_mb_analyse(const TickArgs t) {
 // workgroup) in ONE launch of small workgroups -- instead of k_mb_analyse's 512-thread, 78 KB LDS
 // workgroups followed by k_mb_intra8 -- so the two independent decisions share the CUs (eight
 // workgroups per CU): blocks [0, nRg) the intra roles (longest, first), then the Intra8x8 blocks.
-#ifndef JMH_INTRA_OCC
-#define JMH_INTRA_OCC 8                       // waves per SIMD the register budget targets (A/B: -D)
-#endif
+#define JMH_INTRA_OCC 8                       // waves per SIMD the register budget targets
 template <class pel>
 __global__ __launch_bounds__(NT, JMH_INTRA_OCC) void k_mb_intra(const TickArgs t) {
     __shared__ union {
@@ -1108,8 +1020,8 @@ hipError_t jmh_launch_intra(const TickArgs &t, hipStream_t st) {
 }
 
 hipError_t jmh_launch_analyse(const TickArgs &t, hipStream_t st) {
-    const int nPm = t.me_in_analyse ? t.pre[t.nP] : 0;   // JMH_I4WAVE: their intra decisions ran on wave 7
-    const int nblocks = xcd_grid(nPm) + (t.pre[t.npic] - (JMH_I4WAVE ? nPm : 0) + 3) / 4;
+    const int nPm = t.me_in_analyse ? t.pre[t.nP] : 0;
+    const int nblocks = xcd_grid(nPm) + (t.pre[t.npic] + 3) / 4;
     if (nblocks == 0) return hipSuccess;
     hipLaunchKernelGGL(k_mb_analyse, dim3(nblocks), dim3(NTA), 0, st, t);
     return hipGetLastError();
@@ -1187,14 +1099,6 @@ __device__ __forceinline__ bool flow_done(const FlowArgs &f, int e, int mb, uint
     return __hip_atomic_load(f.flags + (size_t)e * f.nmb + mb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= gen;
 }
 
-// Persistent: every workgroup claims tickets until the segment is exhausted.  Per macroblock: its
-// left and top-right (top at the right edge) neighbours and the reference picture's MB (x+5, y+5)
-// (PIPE_LAG's reach, clamped) must be done -- the rest of the wavefront's dependencies follow from
-// theirs; then the P macroblock's me_mb (41 searches + Intra4x4), its Intra16x16 / chroma
-// decisions on waves 0 / 1 (or an I macroblock's intra_role), and final_core on all 512 threads.
-// Publication: every wave's stores drained, the workgroup barrier, one agent-scope release, the
-// flag; a waiter polls relaxed, then one agent-scope acquire before the workgroup reads
-// (MI355X_MICROARCH.md, inter-workgroup visibility).
 // One workgroup per macroblock of the segment (grid = the segment's MB count), which claims its
 // macroblock by an atomic ticket when it starts, so the MBs run in tick order as the hardware
 // dispatches workgroups into freed slots.  Per macroblock: its left and top-right (top at the

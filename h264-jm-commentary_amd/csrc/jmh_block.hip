@@ -15,6 +15,7 @@
 //     quarter samples computed from the reference (qpel_direct), SATD, LDS candidate sums, the
 //     candidate scan with strict '<' on one thread (JM order).
 #include "jmh_common.h"
+#include "jmh_launch.h"
 
 #define BKOFF 8192                       // cost offset: the zero-vector bias can make a cost negative
 
@@ -113,13 +114,13 @@ __global__ __launch_bounds__(256) void k_block_search(const jmh_block_search *re
     }
 }
 
-hipError_t jmh_launch_block_search(int n, const jmh_block_search *reqs, jmh_block_result *out, const uint8_t *cur, const uint8_t *ref, int W,
-                                   int H, int had, hipStream_t st) {
-    hipLaunchKernelGGL(k_block_search<uint8_t>, dim3(n), dim3(256), 0, st, reqs, out, cur, ref, W, H, had, 255);
+template <class pel>
+hipError_t jmh_launch_block_search(int n, const jmh_block_search *reqs, jmh_block_result *out, const pel *cur, const pel *ref, int W, int H,
+                                   int had, int maxv, hipStream_t st) {
+    hipLaunchKernelGGL(k_block_search<pel>, dim3(n), dim3(256), 0, st, reqs, out, cur, ref, W, H, had, maxv);
     return hipGetLastError();
 }
-hipError_t jmh_launch_block_search_u16(int n, const jmh_block_search *reqs, jmh_block_result *out, const uint16_t *cur, const uint16_t *ref,
-                                       int W, int H, int had, int bit_depth, hipStream_t st) {
-    hipLaunchKernelGGL(k_block_search<uint16_t>, dim3(n), dim3(256), 0, st, reqs, out, cur, ref, W, H, had, (1 << bit_depth) - 1);
-    return hipGetLastError();
-}
+template hipError_t jmh_launch_block_search<uint8_t>(int, const jmh_block_search *, jmh_block_result *, const uint8_t *, const uint8_t *, int, int,
+                                                     int, int, hipStream_t);
+template hipError_t jmh_launch_block_search<uint16_t>(int, const jmh_block_search *, jmh_block_result *, const uint16_t *, const uint16_t *, int,
+                                                      int, int, int, hipStream_t);

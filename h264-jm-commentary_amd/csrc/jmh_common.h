@@ -140,26 +140,15 @@ __device__ __forceinline__ uint32_t lds_u32_any(const void *p) {
 // the compiler folds the move into the consuming v_add / v_sub / v_min as a DPP operand, one
 // instruction instead of a copy, a v_mov_dpp and the operation.  Every caller runs its rows fully
 // active (a lane's result is used only where every lane its reduction reads was active).
-#ifndef JMH_DPP_FOLD
-#define JMH_DPP_FOLD 1                        // A/B: 0 = the earlier update_dpp(v, v) moves
-#endif
 template <int CTRL>
 __device__ __forceinline__ int dpp(int v) {
-#if JMH_DPP_FOLD
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-#else
-    return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false);
-#endif
 }
 // min(v, v of the DPP source lane) with 0xFFFFFFFF as the old value: folds into v_min_u32_dpp, and
 // a disabled source lane leaves v unchanged
 template <int CTRL>
 __device__ __forceinline__ unsigned dpp_umin(unsigned v) {
-#if JMH_DPP_FOLD
     return min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, 0xF, 0xF, false));
-#else
-    return min(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false));
-#endif
 }
 // sum over each aligned 16-lane row (all 16 lanes must be active); every lane gets the sum
 __device__ __forceinline__ int row16_sum(int v) {
@@ -221,40 +210,23 @@ __device__ __forceinline__ int inv_tap(int e0, int e1, int e2, int e3, int k) {
     const int a = outer ? e0 : e1, b = outer ? e3 : e2;
     return k < 2 ? a + b : a - b;
 }
-#ifndef JMH_LANE_TAPS
-#define JMH_LANE_TAPS 1                       // A/B: 0 = the ?: chains in lane_fwd4x4 / lane_inv4x4
-#endif
 // forward 4x4 core transform (dct_luma [J]): rows then columns
 __device__ __forceinline__ int lane_fwd4x4(int r, int l) {
     int y = l >> 2, x = l & 3;
     int v0 = g16(r, 4 * y), v1 = g16(r, 4 * y + 1), v2 = g16(r, 4 * y + 2), v3 = g16(r, 4 * y + 3);
     int p0 = v0 + v3, p3 = v0 - v3, p1 = v1 + v2, p2 = v1 - v2;
-#if JMH_LANE_TAPS
     const int t = fwd_tap(p0, p1, p2, p3, x);
     const int u0 = g16(t, x), u1 = g16(t, 4 + x), u2 = g16(t, 8 + x), u3 = g16(t, 12 + x);
     return fwd_tap(u0 + u3, u1 + u2, u1 - u2, u0 - u3, y);
-#else
-    int t = x == 0 ? p0 + p1 : x == 1 ? 2 * p3 + p2 : x == 2 ? p0 - p1 : p3 - 2 * p2;
-    int u0 = g16(t, x), u1 = g16(t, 4 + x), u2 = g16(t, 8 + x), u3 = g16(t, 12 + x);
-    p0 = u0 + u3; p3 = u0 - u3; p1 = u1 + u2; p2 = u1 - u2;
-    return y == 0 ? p0 + p1 : y == 1 ? 2 * p3 + p2 : y == 2 ? p0 - p1 : p3 - 2 * p2;
-#endif
 }
 // inverse 4x4 (8.5.12.2, rows first) + reconstruction clip((x + (pred << 6) + 32) >> 6) to maxv
 __device__ __forceinline__ int lane_inv4x4(int dq, int l, int pred, int maxv = 255) {
     int y = l >> 2, x = l & 3;
     int d0 = g16(dq, 4 * y), d1 = g16(dq, 4 * y + 1), d2 = g16(dq, 4 * y + 2), d3 = g16(dq, 4 * y + 3);
     int e0 = d0 + d2, e1 = d0 - d2, e2 = (d1 >> 1) - d3, e3 = d1 + (d3 >> 1);
-#if JMH_LANE_TAPS
     const int t = inv_tap(e0, e1, e2, e3, x);
     const int f0 = g16(t, x), f1 = g16(t, 4 + x), f2 = g16(t, 8 + x), f3 = g16(t, 12 + x);
     const int o = inv_tap(f0 + f2, f0 - f2, (f1 >> 1) - f3, f1 + (f3 >> 1), y);
-#else
-    int t = x == 0 ? e0 + e3 : x == 1 ? e1 + e2 : x == 2 ? e1 - e2 : e0 - e3;
-    int f0 = g16(t, x), f1 = g16(t, 4 + x), f2 = g16(t, 8 + x), f3 = g16(t, 12 + x);
-    e0 = f0 + f2; e1 = f0 - f2; e2 = (f1 >> 1) - f3; e3 = f1 + (f3 >> 1);
-    int o = y == 0 ? e0 + e3 : y == 1 ? e1 + e2 : y == 2 ? e1 - e2 : e0 - e3;
-#endif
     return iclip(0, maxv, (o + (pred << 6) + 32) >> 6);
 }
 // quantisation rounding offset at q_bits (docs/JM_SEMANTICS.md items 1 and 45; oracle jmo_qround):

@@ -10,22 +10,10 @@
 #define QPAD 4                           // quarter-pel plane padding (== oracle JMO_PAD)
 #define NT 256                           // threads per finalize / unit workgroup
 #define NTA 512                          // threads per analysis workgroup (8 waves, 2 per SIMD)
-// JMH_I4WAVE 1: a P macroblock's intra decisions run on wave 7 of its motion-search workgroup on
-// their own schedule (the seven search waves meet at LDS-counter barriers, never at s_barrier, which
-// would wait for wave 7), so the Intra4x4 chain is off the search's stage chain; 0: the Intra4x4
-// steps ride in the stages' sub-pel phases on waves 6 and 7 (A/B: -DJMH_I4WAVE=0).  The variant
-// measured slower (1143 vs 1168 MP/s, profiles/r8a_i4wave_ab.txt) and is kept for A/B only: it is
-// correct only while intra_wave and every search stage after the split are free of __syncthreads
-// (an s_barrier would pair arrivals of unrelated program points), and no test builds it.
-#ifndef JMH_I4WAVE
-#define JMH_I4WAVE 0
-#endif
-#if JMH_I4WAVE && !defined(JMH_I4WAVE_AB)
-#error "JMH_I4WAVE is an A/B-only variant: define JMH_I4WAVE_AB to build it (see the comment above)"
-#endif
-#define NTS (JMH_I4WAVE ? 448 : NTA)     // threads of the FFS position strips (the search waves)
-#define NPK (JMH_I4WAVE ? 11 : 10)       // FFS search positions per search thread (a column strip):
-                                         //   65 x ceil(65 / NPK) strips <= NTS
+// (a P macroblock's Intra4x4 steps ride in the search stages' sub-pel phases on waves 6 and 7; a
+// variant with the intra decisions on a wave of their own measured slower)
+#define NPK 10                           // FFS search positions per thread (a column strip):
+                                         //   65 x ceil(65 / NPK) strips <= NTA
 #define NPK2 ((NPK + 1) / 2)             // packed order-key pairs per thread
 #define ORDTAB_SPOS (NPK2 * NTA)         // ordtab: the spiral-index -> position table after the keys
 #define BIGCOST (1 << 20)

@@ -10,27 +10,16 @@ __device__ __forceinline__ int wcost(const DevParams &d, int bits) {
 }
 
 #define NTE 64                                // one wave per macroblock
-#ifndef EOFF_L                                // (-DEOFF_L=...: A/B builds)
 #define EOFF_L 48                             // LDS window margin around the MB (or 2 SR + 4 if less;
                                               //   A/B on config 3: profiles/r7j_window_ab.txt)
-#endif
 // window loads in flight per lane (one batch of global loads per round trip)
-#ifndef EPZS_NB8
 #define EPZS_NB8 32
-#endif
-#ifndef EPZS_NB16
 #define EPZS_NB16 16
-#endif
-#ifndef EPZS_FB_ROWS
 #define EPZS_FB_ROWS 4                        // k_rdo_inter: block rows per batch of global loads when a SAD
-#endif                                        //   leaves the window (k_mb_epzs: 1; A/B profiles/r7x_fallback_ab.txt)
-#ifndef EPZS_EDGE
-#define EPZS_EDGE 0                           // samples a window SAD needs right of its block: none -- the extra
-#endif                                        //   dword a row reads for v_alignbyte only feeds unused bytes, and
-                                              //   past the window's last row it stays inside EpzS (gn follows g)
-#ifndef EOFF_L16
+                                              //   leaves the window (k_mb_epzs: 1; A/B profiles/r7x_fallback_ab.txt)
+// (a window SAD needs no sample right of its block: the extra dword a row reads for v_alignbyte only
+// feeds unused bytes, and past the window's last row it stays inside EpzS, gn follows g)
 #define EOFF_L16 40                           // ... for 16-bit samples: 30.4 KB k_rdo_inter, five MBs per CU (A/B: profiles/r5r_window_ab.txt)
-#endif
 // window geometry per sample type: margin, rows (= row stride) of the LDS window
 template <class pel>
 struct EGeo {
@@ -224,7 +213,7 @@ __device__ __forceinline__ unsigned lane_block_sad(const EpzS<pel> &s, const EWi
     uint32_t sad = 0;
     if constexpr (sizeof(pel) == 2) {
         constexpr int ND = 2 * W4;            // dwords of a block row
-        if (gx >= 0 && gx + 4 * W4 + EPZS_EDGE <= EGeo<pel>::ew && gy >= 0 && gy + H <= EGeo<pel>::ew) {
+        if (gx >= 0 && gx + 4 * W4 <= EGeo<pel>::ew && gy >= 0 && gy + H <= EGeo<pel>::ew) {
             const int a = gy * EGeo<pel>::ew + gx;
             const uint32_t sel = (uint32_t)(a & 1) * 2;
             const uint32_t *base = reinterpret_cast<const uint32_t *>(s.g + (a & ~1));
@@ -253,7 +242,7 @@ __device__ __forceinline__ unsigned lane_block_sad(const EpzS<pel> &s, const EWi
         }
         return sad;
     }
-    if (gx >= 0 && gx + 4 * W4 + EPZS_EDGE <= EGeo<pel>::ew && gy >= 0 && gy + H <= EGeo<pel>::ew) {   // inside the window
+    if (gx >= 0 && gx + 4 * W4 <= EGeo<pel>::ew && gy >= 0 && gy + H <= EGeo<pel>::ew) {   // inside the window
         const int a = gy * EGeo<pel>::ew + gx;
         const uint32_t sel = (uint32_t)(a & 3);
         const uint32_t *base = reinterpret_cast<const uint32_t *>(s.g + (a & ~3));
@@ -403,12 +392,8 @@ __device__ __forceinline__ void ffs_table_build(const DevParams &d, const EpzS<p
 // 64 (SR 32) of those rows on lanes 0 .. FFS_RB - 1.  The entry's halves summed per selector class
 // M (uniform): 0 all four (uint2, two v_sad_u16), 1 one dword's pair (u32, one v_sad_u16), 2 halves
 // 0 + 2 or 1 + 3 (uint2, v_perm + v_sad_u16), 3 one half (u32, one shift or mask).
-#ifndef FFS_RB
 #define FFS_RB 22                                     // rows per round trip, 8-byte entries (M 0, 2)
-#endif
-#ifndef FFS_RB4
 #define FFS_RB4 22                                    // ... 4-byte reads (M 1, 3)
-#endif
 template <int M>
 __device__ __forceinline__ unsigned ffs_min_m(const DevParams &d, const uint8_t *tab_, int ph, int sel, int range, int ccx, int ccy, int pmx, int pmy, int lane) {
     const int R = d.sr, side = 2 * R + 1, np = side * side, n = 2 * range + 1, c0 = R - range;
@@ -476,9 +461,8 @@ __device__ __forceinline__ unsigned ffs_table_min(const DevParams &d, const uint
 // right, 4x4 #1), equal ranges (RestrictSearchRange != 0).  Search k of SET 0 sums all four halves,
 // the low dword's pair, halves 0 + 2, half 0; of SET 1 the high dword's pair, halves 1 + 3, half 1.
 // Keys as ffs_table_min (the argmin is bound by its round trips: one pass serves NS searches)
-#ifndef FFS_GRB
 #define FFS_GRB 13                                   // rows per round trip of a grouped pass (5 at SR 32: fewer
-#endif                                               //   live registers beat fewer trips, profiles/r11a)
+                                                     //   live registers beat fewer trips, profiles/r11a)
 template <int NS, int SET = 0>
 __device__ __forceinline__ void ffs_group_min(const DevParams &d, const uint8_t *tab_, int ph, int range, int ccx, int ccy, const int (&pmx)[4],
                                               const int (&pmy)[4], int lane, unsigned (&kb)[4]) {

@@ -27,6 +27,7 @@
 // for the SADs, the packed-int16 Hadamard on 16-bit differences (|d| <= 1023 keeps every stage in
 // range), int32 horizontal taps, and the EPZS thresholds times 1 << (BitDepthY - 8).
 #include "jmh_epzs.h"
+#include "jmh_launch.h"
 
 // JM10X: built with JM >= 10's EPZS options (EPZSDualRefinement, EPZSSubPelME, the adaptive
 // thresholds: items 46, 61, 62); the instantiation without them (all off, e.g. config 3's JM 8.6

@@ -5,6 +5,7 @@
 // or, with Transform8x8Mode, TransformDecision and dct_luma8x8 on one wave per 8x8 block, and the
 // outputs the next diagonal depends on (reconstruction, MVs, reference indices, intra modes).
 #include "jmh_final.h"
+#include "jmh_launch.h"
 
 // OCC workgroups per CU (see jmh_final.h)
 template <int OCC, class pel, bool T8>
@@ -27,13 +28,11 @@ __global__ __launch_bounds__(2 * NT, 4) void k_mb_final512(const TickArgs t) {
 }
 
 hipError_t jmh_launch_final(const TickArgs &t, hipStream_t st) {
-    static const bool occ8 = getenv("JMH_FINAL_OCC8") != nullptr;   // A/B: the 8-per-CU build always
-    static const char *f512 = getenv("JMH_FINAL512");               // A/B: 0 = the 256-thread five-per-CU build
     const int n = t.pre[t.npic];
-    if (!occ8 && t.bd == 8 && !t.t8 && n <= 2 * 256 && !(f512 && atoi(f512) == 0))
+    if (t.bd == 8 && !t.t8 && n <= 2 * 256)
         hipLaunchKernelGGL((k_mb_final512<uint8_t, false>), dim3(xcd_grid(n)), dim3(2 * NT), 0, st, t);
     else if (t.bd > 8) hipLaunchKernelGGL((k_mb_final<8, uint16_t, true>), dim3(xcd_grid(n)), dim3(NT), 0, st, t);
-    else if (occ8 || n > 5 * 256) hipLaunchKernelGGL((k_mb_final<8, uint8_t, true>), dim3(xcd_grid(n)), dim3(NT), 0, st, t);
+    else if (n > 5 * 256) hipLaunchKernelGGL((k_mb_final<8, uint8_t, true>), dim3(xcd_grid(n)), dim3(NT), 0, st, t);
     else if (t.t8) hipLaunchKernelGGL((k_mb_final<5, uint8_t, true>), dim3(xcd_grid(n)), dim3(NT), 0, st, t);
     else hipLaunchKernelGGL((k_mb_final<5, uint8_t, false>), dim3(xcd_grid(n)), dim3(NT), 0, st, t);
     return hipGetLastError();

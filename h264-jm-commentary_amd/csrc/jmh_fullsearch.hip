@@ -22,6 +22,7 @@
 // 1.. -- and no 16x16 zero-vector bias in full pel).  8-bit FFS keeps k_mb_analyse's shared 4x4
 // SAD table; here each search sums its block directly (7x the SAD work, on the 10-bit path only).
 #include "jmh_common.h"
+#include "jmh_launch.h"
 
 #define NTF 256                               // threads per full-search workgroup
 #define FOFF_MAX (2 * SRMAX + 4)              // window margin around the MB

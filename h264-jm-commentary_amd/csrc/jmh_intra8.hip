@@ -10,6 +10,7 @@
 // sample of the 8x8 block (64-lane Hadamard by lane exchanges), and wave 0 transforms the winner.
 // Results land in MbScratch (i8cost, i8cbp, i8modes, i8lev, i8rec) for k_mb_final's decision.
 #include "jmh_intra8.h"
+#include "jmh_launch.h"
 
 __global__ __launch_bounds__(NT, 8) void k_mb_intra8(const TickArgs t) {
     __shared__ I8S<uint8_t> s;   // bit depth 8 (FFS / full-search ticks)

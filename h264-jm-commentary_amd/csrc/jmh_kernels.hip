@@ -5,11 +5,20 @@
 //                for the jmh_read_qpel seam (a1).  The macroblock kernels interpolate on the fly
 //                (LDS planes in k_mb_analyse, qpel_direct in k_mb_final), so a picture can be
 //                searched while its reference is still being reconstructed (pipelining).
-//  k_sad_table / k_tq4x4   unit seams (jmh_ffs_sad_table / jmh_tq4x4_batch); k_tq4x4 runs the
-//                same 16-lane TQ primitive the macroblock kernels use.
+//  k_sad_table / k_tq4x4 / k_tq8x8   unit seams, one template each on the sample type: uint8_t, and
+//                uint16_t for the High 10 seams (9 / 10-bit luma, config 5; include/jmhip.h
+//                jmh_*_u16; JM >= 10 FRExt with imgpel = unsigned short [J]):
+//    k_sad_table  SetupFastFullPelSearch's 4x4 BlockSAD table: one thread per (macroblock, window
+//                 position); a 4x4 SAD <= 16 * 1023 fits the u16 table at 10 bits as at 8
+//    k_tq4x4      dct_luma at qp + QpBdOffsetY on 16-lane groups (the macroblock kernels'
+//                 lane_fwd4x4 / lane_quant / lane_inv4x4), reconstruction clipped to 2^bd - 1
+//    k_tq8x8      dct_luma8x8 likewise on one wave per block; int32 headroom at 10 bits: the
+//                 largest |coefficient| x quant_coef8 is 64 * 1023 * 20972 + (1 << 26) / 3 < 2^31
+//                The per-block search seam is k_block_search (jmh_block.hip).
 //
 // The macroblock wavefront itself is k_mb_analyse (jmh_analyse.hip) + k_mb_final (jmh_final.hip).
 #include "jmh_common.h"
+#include "jmh_launch.h"
 
 // ======================================================================================
 //  quarter-pel interpolation (H.264 8.4.2.2.1), spec coordinate clamping
@@ -41,9 +50,10 @@ __global__ __launch_bounds__(256) void k_interp(const uint8_t *__restrict__ ref,
 }
 
 // ======================================================================================
-//  unit seams
+//  unit seams (pel: uint8_t or uint16_t samples; qpb = qp + QpBdOffset, maxv = 2^bd - 1)
 // ======================================================================================
-__global__ __launch_bounds__(256) void k_sad_table(const uint8_t *__restrict__ org, const uint8_t *__restrict__ ref, int W, int H, int sr,
+template <class pel>
+__global__ __launch_bounds__(256) void k_sad_table(const pel *__restrict__ org, const pel *__restrict__ ref, int W, int H, int sr,
                                                    const int32_t *mb_xy, const int32_t *centres, uint16_t *out) {
     int i = blockIdx.y;
     int side = 2 * sr + 1, npos = side * side;
@@ -61,33 +71,35 @@ __global__ __launch_bounds__(256) void k_sad_table(const uint8_t *__restrict__ o
 }
 
 // the macroblock kernel's 16-lane dct_luma on independent blocks (16 lanes per block)
-__global__ __launch_bounds__(256) void k_tq4x4(int n, const int16_t *resid, const uint8_t *pred, int qp, int qsel, int16_t *levels,
-                                               uint8_t *recon, int32_t *coeff_cost, int32_t *nonzero) {
+template <class pel>
+__global__ __launch_bounds__(256) void k_tq4x4(int n, const int16_t *resid, const pel *pred, int qpb, int qsel, int maxv, int16_t *levels,
+                                               pel *recon, int32_t *coeff_cost, int32_t *nonzero) {
     const int blk = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
     const bool act = blk < n;
     const int bi = act ? blk : 0;
     const int c = lane_fwd4x4(resid[16 * bi + l], l);
     int lev, dq, cc;
-    const int q_bits = 15 + qp / 6;
-    unsigned nz = lane_quant(c, l, qp, q_round(qsel, q_bits), false, lev, dq, cc);
-    const int rv = lane_inv4x4(dq, l, pred[16 * bi + l]);
+    const int q_bits = 15 + qpb / 6;
+    unsigned nz = lane_quant(c, l, qpb, q_round(qsel, q_bits), false, lev, dq, cc);
+    const int rv = lane_inv4x4(dq, l, pred[16 * bi + l], maxv);
     if (act) {
         levels[16 * blk + l] = (int16_t)lev;
-        recon[16 * blk + l] = (uint8_t)rv;
+        recon[16 * blk + l] = (pel)rv;
         if (l == 0) { coeff_cost[blk] = cc; nonzero[blk] = nz != 0; }
     }
 }
 
 // the macroblock kernels' one-wave dct_luma8x8 on independent blocks (4 blocks per workgroup)
-__global__ __launch_bounds__(256) void k_tq8x8(int n, const int16_t *resid, const uint8_t *pred, int qp, int qsel, int16_t *levels,
-                                               uint8_t *recon, int32_t *coeff_cost, int32_t *nonzero) {
+template <class pel>
+__global__ __launch_bounds__(256) void k_tq8x8(int n, const int16_t *resid, const pel *pred, int qpb, int qsel, int maxv, int16_t *levels,
+                                               pel *recon, int32_t *coeff_cost, int32_t *nonzero) {
     const int blk = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
     if (blk >= n) return;                        // whole waves only: no workgroup barrier below
-    const int q_bits = 16 + qp / 6;
+    const int q_bits = 16 + qpb / 6;
     const int c = wave_fwd8x8(resid[64 * blk + l], l);
     int lev, dq, cc;
-    const unsigned long long nz = wave_quant8(c, l, qp, q_round(qsel, q_bits), lev, dq, cc);
-    recon[64 * blk + l] = (uint8_t)wave_inv8x8(dq, l, pred[64 * blk + l]);
+    const unsigned long long nz = wave_quant8(c, l, qpb, q_round(qsel, q_bits), lev, dq, cc);
+    recon[64 * blk + l] = (pel)wave_inv8x8(dq, l, pred[64 * blk + l], maxv);
     levels[64 * blk + l] = (int16_t)lev;
     if (l == 0) { coeff_cost[blk] = cc; nonzero[blk] = nz != 0; }
 }
@@ -98,19 +110,30 @@ hipError_t jmh_launch_interp(const uint8_t *ref, int W, int H, uint8_t *qpel, in
     hipLaunchKernelGGL(k_interp, grid, dim3(256), 0, st, ref, W, H, qpel, qstride, qplane);
     return hipGetLastError();
 }
-hipError_t jmh_launch_sad_table(const uint8_t *org, const uint8_t *ref, int W, int H, int sr, int n_mb, const int32_t *mb_xy,
-                                const int32_t *centres, uint16_t *out, hipStream_t st) {
+template <class pel>
+hipError_t jmh_launch_sad_table(const pel *org, const pel *ref, int W, int H, int sr, int n_mb, const int32_t *mb_xy, const int32_t *centres,
+                                uint16_t *out, hipStream_t st) {
     int side = 2 * sr + 1, npos = side * side;
-    hipLaunchKernelGGL(k_sad_table, dim3((npos + 255) / 256, n_mb), dim3(256), 0, st, org, ref, W, H, sr, mb_xy, centres, out);
+    hipLaunchKernelGGL(k_sad_table<pel>, dim3((npos + 255) / 256, n_mb), dim3(256), 0, st, org, ref, W, H, sr, mb_xy, centres, out);
     return hipGetLastError();
 }
-hipError_t jmh_launch_tq8x8(int n, const int16_t *resid, const uint8_t *pred, int qp, int qsel, int16_t *levels, uint8_t *recon,
+template <class pel>
+hipError_t jmh_launch_tq4x4(int n, const int16_t *resid, const pel *pred, int qpb, int qsel, int maxv, int16_t *levels, pel *recon,
                             int32_t *cc, int32_t *nz, hipStream_t st) {
-    hipLaunchKernelGGL(k_tq8x8, dim3((n + 3) / 4), dim3(256), 0, st, n, resid, pred, qp, qsel, levels, recon, cc, nz);
+    hipLaunchKernelGGL(k_tq4x4<pel>, dim3((n + 15) / 16), dim3(256), 0, st, n, resid, pred, qpb, qsel, maxv, levels, recon, cc, nz);
     return hipGetLastError();
 }
-hipError_t jmh_launch_tq4x4(int n, const int16_t *resid, const uint8_t *pred, int qp, int qsel, int16_t *levels, uint8_t *recon,
+template <class pel>
+hipError_t jmh_launch_tq8x8(int n, const int16_t *resid, const pel *pred, int qpb, int qsel, int maxv, int16_t *levels, pel *recon,
                             int32_t *cc, int32_t *nz, hipStream_t st) {
-    hipLaunchKernelGGL(k_tq4x4, dim3((n + 15) / 16), dim3(256), 0, st, n, resid, pred, qp, qsel, levels, recon, cc, nz);
+    hipLaunchKernelGGL(k_tq8x8<pel>, dim3((n + 3) / 4), dim3(256), 0, st, n, resid, pred, qpb, qsel, maxv, levels, recon, cc, nz);
     return hipGetLastError();
 }
+#define JMH_SEAMS(pel)                                                                                                                  \
+    template hipError_t jmh_launch_sad_table<pel>(const pel *, const pel *, int, int, int, int, const int32_t *, const int32_t *, uint16_t *, \
+                                                  hipStream_t);                                                                         \
+    template hipError_t jmh_launch_tq4x4<pel>(int, const int16_t *, const pel *, int, int, int, int16_t *, pel *, int32_t *, int32_t *, hipStream_t); \
+    template hipError_t jmh_launch_tq8x8<pel>(int, const int16_t *, const pel *, int, int, int, int16_t *, pel *, int32_t *, int32_t *, hipStream_t);
+JMH_SEAMS(uint8_t)
+JMH_SEAMS(uint16_t)
+#undef JMH_SEAMS

@@ -21,6 +21,7 @@
 // docs/JM_SEMANTICS.md items 53-60, 63 and 64 pin every RD choice.
 #include <type_traits>
 #include "jmh_epzs.h"
+#include "jmh_launch.h"
 #include "jmh_intra.h"
 #include "jmh_deblock.h"
 // Table 9-44 in LDS for every kernel of this file that codes bins (filled by jmr_lds_tables_load)
@@ -1014,9 +1015,8 @@ __device__ __forceinline__ void rdo_intra_mb(const DevParams &d, RdoIntraS<pel, 
     PSTAMP(61);
 }
 
-#ifndef JMH_RDO_INTER_WPE
 #define JMH_RDO_INTER_WPE 1                   // waves per SIMD the register budget must allow (2: five per CU
-#endif                                        //   at 16 bits, 32 B of scratch, 10 % slower: profiles/r7x_fallback_ab.txt)
+                                              //   at 16 bits, 32 B of scratch, 10 % slower: profiles/r7x_fallback_ab.txt)
 template <class pel, bool T8, bool FFS>
 __global__ __launch_bounds__(NTE, JMH_RDO_INTER_WPE) void k_rdo_inter(const TickArgs t) {
     __shared__ RdoInterS<pel> s;
@@ -1097,9 +1097,8 @@ struct RdoFinS {
 
 // T8: Transform8x8Mode (the 8x8-transform and I8MB candidates; jmr_mb's 8x8 residual path); CAV:
 // SymbolMode 0 (jmv_mb rates, the slice's mb_skip_run)
-#ifndef JMH_RDO_FINAL_WPE
 #define JMH_RDO_FINAL_WPE 5                   // Transform8x8Mode: waves per SIMD the register budget must allow
-#endif                                        //   (the 8x8 CABAC residual path would take 146 VGPRs: three)
+                                              //   (the 8x8 CABAC residual path would take 146 VGPRs: three)
 template <class pel, bool T8, bool CAV>
 __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(const TickArgs t) {
     __shared__ RdoFinS<pel> s;

@@ -19,35 +19,8 @@
 #include <deque>
 #include <vector>
 #include <algorithm>
-#include "jmh_device.h"
+#include "jmh_launch.h"
 #include "jmh_cabac_rate.h"
-
-hipError_t jmh_launch_interp(const uint8_t *ref, int W, int H, uint8_t *qpel, int qstride, int qplane, hipStream_t st);
-hipError_t jmh_launch_analyse(const TickArgs &t, hipStream_t st);
-hipError_t jmh_launch_intra(const TickArgs &t, hipStream_t st);
-hipError_t jmh_launch_final(const TickArgs &t, hipStream_t st);
-hipError_t jmh_launch_intra8(const TickArgs &t, hipStream_t st);
-hipError_t jmh_launch_me_full(const TickArgs &t, hipStream_t st);
-hipError_t jmh_launch_epzs(const TickArgs &t, hipStream_t st);
-hipError_t jmh_launch_flow(const FlowArgs &f, hipStream_t st);
-hipError_t jmh_launch_rdo(const TickArgs &t, hipStream_t st, hipStream_t side, hipEvent_t fork, hipEvent_t join);
-size_t jmh_rdo_scratch_bytes();
-hipError_t jmh_launch_block_search_u16(int n, const jmh_block_search *reqs, jmh_block_result *out, const uint16_t *cur, const uint16_t *ref,
-                                       int W, int H, int had, int bit_depth, hipStream_t st);
-hipError_t jmh_launch_sad_table_u16(const uint16_t *org, const uint16_t *ref, int W, int H, int sr, int n_mb, const int32_t *mb_xy,
-                                    const int32_t *centres, uint16_t *out, hipStream_t st);
-hipError_t jmh_launch_tq4x4_u16(int n, const int16_t *resid, const uint16_t *pred, int qp, int qsel, int bit_depth, int16_t *levels,
-                                uint16_t *recon, int32_t *cc, int32_t *nz, hipStream_t st);
-hipError_t jmh_launch_tq8x8_u16(int n, const int16_t *resid, const uint16_t *pred, int qp, int qsel, int bit_depth, int16_t *levels,
-                                uint16_t *recon, int32_t *cc, int32_t *nz, hipStream_t st);
-hipError_t jmh_launch_sad_table(const uint8_t *org, const uint8_t *ref, int W, int H, int sr, int n_mb, const int32_t *mb_xy,
-                                const int32_t *centres, uint16_t *out, hipStream_t st);
-hipError_t jmh_launch_tq8x8(int n, const int16_t *resid, const uint8_t *pred, int qp, int qsel, int16_t *levels, uint8_t *recon,
-                            int32_t *cc, int32_t *nz, hipStream_t st);
-hipError_t jmh_launch_block_search(int n, const jmh_block_search *reqs, jmh_block_result *out, const uint8_t *cur, const uint8_t *ref, int W,
-                                   int H, int had, hipStream_t st);
-hipError_t jmh_launch_tq4x4(int n, const int16_t *resid, const uint8_t *pred, int qp, int qsel, int16_t *levels, uint8_t *recon,
-                            int32_t *cc, int32_t *nz, hipStream_t st);
 
 // quantisation rounding selector of a slice (q_round, jmh_common.h; docs/JM_SEMANTICS.md items 1
 // and 45): JM 8.6 = 1 in I slices, 0 in P slices; JMVersion >= 10 = 2 + the slice's OffsetMatrix entry
@@ -142,16 +115,16 @@ struct jmh_ctx {
     int dev;
     hipStream_t st;                      // the wavefront ticks (and source uploads)
     hipStream_t cst;                     // readback of finished pictures, overlapping later ticks
-    hipStream_t sst = nullptr;           // RDO on: k_rdo_intra beside k_rdo_inter (JMH_RDO_SIDE=0: off)
+    hipStream_t sst = nullptr;           // RDO on: k_rdo_intra beside k_rdo_inter
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int W, H, Wc, Hc, mbw, mbh, sr, side, npos, qstride, qplane, nd;
     size_t fsize, n4, nmb;               // bytes of one 4:2:0 picture (Y then U then V)
     uint8_t *d_ref, *d_qpel, *d_slots;   // explicit reference (set_reference), a1 seam, slots
-    uint8_t *d_scur, *d_sref;            // luma pictures of the per-block searches (jmh_search_pictures)
+    struct { void *cur, *ref; } spic[2]; // luma pictures of the per-block searches, by sample width: [0] 8-bit
+                                         //   (jmh_search_pictures), [1] 16-bit, the High 10 seams (..._u16)
     uint32_t *d_ordtab;                  // FFS order keys of the analysis threads' strips (ordtab_fill)
-    uint16_t *d_scur16, *d_sref16;       // 16-bit luma pictures of the High 10 seams (jmh_search_pictures_u16)
     int bd, ps, maxv;                    // picture bit depth, bytes per sample (1, 2), (1 << bd) - 1
-    int hbd_bits;                        //   and their bit depth
+    int hbd_bits;                        // bit depth of the 16-bit search pictures
     int nslots;
     int depth, nring;
     std::vector<PicBuf> ring;
@@ -181,7 +154,8 @@ struct jmh_ctx {
     // collected into a segment of macroblocks in tick order, launched as one grid on a flush
     bool flow = false;
     int seg_max = 0;                     // ticks per segment before a flush (JMH_FLOW_SEG)
-    int seg_min = 0;                     // ... or, once the device is idle, this many (JMH_FLOW_SEG_MIN)
+    int seg_min = 8;                     // ... or, once the device is idle, this many (2 / 4 / 16 within
+                                         //   noise: profiles/r10h_flow_bench20_ab.txt)
     hipEvent_t ev_flow = nullptr;        // the last segment launch's end: a segment of >= seg_min ticks
                                          //   is flushed as soon as the device has run out of work
     std::vector<FlowPic> fpic;           // per ring entry: parameters + flag generations
@@ -365,8 +339,8 @@ void jmh_destroy(jmh_ctx *c) {
     if (c->cst) (void)hipStreamSynchronize(c->cst);
     if (c->sst) (void)hipStreamSynchronize(c->sst);
     for (PicBuf &b : c->ring) free_entry(b);
-    void *dev_bufs[] = {c->d_ref, c->d_qpel, c->d_slots, c->d_prof, c->d_bprof, c->d_scur, c->d_sref, c->d_ordtab, c->d_scur16,
-                        c->d_sref16, c->d_sched, c->d_soff, c->d_rscr, c->d_ffs, c->d_seg[0], c->d_seg[1], c->d_flags, c->d_head,
+    void *dev_bufs[] = {c->d_ref, c->d_qpel, c->d_slots, c->d_prof, c->d_bprof, c->spic[0].cur, c->spic[0].ref, c->d_ordtab, c->spic[1].cur,
+                        c->spic[1].ref, c->d_sched, c->d_soff, c->d_rscr, c->d_ffs, c->d_seg[0], c->d_seg[1], c->d_flags, c->d_head,
                         c->d_fprof};
     for (void *p : dev_bufs) if (p) (void)hipFree(p);
     if (c->h_stage_ref) (void)hipHostFree(c->h_stage_ref);
@@ -448,8 +422,6 @@ int jmh_create(const jmh_config *cfg, int hip_device, jmh_ctx **out) {
                   !(fe && atoi(fe) == 0) &&
                   !getenv("JMH_BLOCK_PROF") && c->mbw < 4096 && c->mbh < 4096;
         const char *sg = getenv("JMH_FLOW_SEG");
-        const char *sm = getenv("JMH_FLOW_SEG_MIN");
-        c->seg_min = sm && atoi(sm) > 0 ? atoi(sm) : 8;
         c->seg_max = sg && atoi(sg) > 0 ? std::min(atoi(sg), 256) : 128;   // (<= 256: nring stays < 64, seg_mask's bits)   // A/B 64 / 128 / 256: 1392.6 / 1402.4 / 1401.4 MP/s (profiles/r10g_flow_seg_ab.txt)
     }
     // (dataflow: enough more entries that an entry's next occupant never falls into a segment that
@@ -467,11 +439,9 @@ int jmh_create(const jmh_config *cfg, int hip_device, jmh_ctx **out) {
         // RDO on: the intra role on a side stream, concurrent with the inter role (the inter
         // workgroups' LDS leaves room for intra ones beside them); joined before k_rdo_final.
         // RDO off with a separate search kernel (EPZS, full search, High 10 FFS): k_mb_intra on the
-        // side stream beside k_mb_epzs / k_mb_me_full, joined before k_mb_final (A/B knobs:
-        // JMH_RDO_SIDE=0, JMH_INTRA_SIDE=0)
-        const char *side = getenv(cfg->rdo ? "JMH_RDO_SIDE" : "JMH_INTRA_SIDE");
+        // side stream beside k_mb_epzs / k_mb_me_full, joined before k_mb_final
         const bool sep_search = cfg->rdo || cfg->search_mode != 0 || (cfg->bit_depth > 8);
-        if (sep_search && !(side && atoi(side) == 0)) {
+        if (sep_search) {
             if (hipStreamCreateWithFlags(&c->sst, hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) { st = JMH_E_HIP; goto fail; }
@@ -539,10 +509,9 @@ int jmh_create(const jmh_config *cfg, int hip_device, jmh_ctx **out) {
             ALLOC(c->d_sched, rd_order.size() * sizeof(int32_t));
             ALLOC(c->d_soff, rd_off.size() * sizeof(int32_t));
             ALLOC(c->d_rscr, (size_t)PMAX * maxc * jmh_rdo_scratch_bytes());
-            // SearchMode 0: one SAD table per tick MB (JMH_RDO_FFS_TABLE=0: every search scans, A/B)
-            const char *ft = getenv("JMH_RDO_FFS_TABLE");
+            // SearchMode 0: one SAD table per tick MB
             // (a failed allocation leaves d_ffs null: the searches then scan, with identical results)
-            if (cfg->search_mode == 0 && !(ft && atoi(ft) == 0) &&
+            if (cfg->search_mode == 0 &&
                 hipMalloc(&c->d_ffs, (size_t)PMAX * maxc * ffs_slot_bytes(c->sr)) != hipSuccess) {
                 c->d_ffs = nullptr;
                 (void)hipGetLastError();
@@ -585,12 +554,12 @@ static int host_spiral_index(int x, int y) {
 
 // order keys of the FFS analysis threads (k_mb_analyse): thread t owns window column t % side,
 // rows (t / side) * NPK .. + NPK - 1; key = spiral index + 1 (0 is the (0,0) pre-check, set per
-// MB in the kernel), 0xFFFF outside the window.  [NPK2][NTA] packed pairs (low = even slot); only
-// the NTS search threads own strips.  Then the inverse, ORDTAB_SPOS: spiral index -> position
+// MB in the kernel), 0xFFFF outside the window.  [NPK2][NTA] packed pairs (low = even slot).  Then
+// the inverse, ORDTAB_SPOS: spiral index -> position
 // (x & 0xFFFF | y << 16), read with one scalar load where a search's winner is decoded.
 static void ordtab_fill(std::vector<uint32_t> &tab, int sr) {
     const int side = 2 * sr + 1, nstrips = (side + NPK - 1) / NPK;
-    static_assert(SIDE_MAX * ((SIDE_MAX + NPK - 1) / NPK) <= NTS, "the search threads cover every FFS position");
+    static_assert(SIDE_MAX * ((SIDE_MAX + NPK - 1) / NPK) <= NTA, "the search threads cover every FFS position");
     // after the keys: spiral index -> position, then raster position -> spiral index (the RDO FFS
     // table's tie order, jmh_epzs.h ffs_table_min)
     tab.assign((size_t)ORDTAB_SPOS + (size_t)2 * side * side, 0);
@@ -600,7 +569,7 @@ static void ordtab_fill(std::vector<uint32_t> &tab, int sr) {
             tab[(size_t)ORDTAB_SPOS + (size_t)side * side + (size_t)(y + sr) * side + x + sr] = (uint32_t)host_spiral_index(x, y);
         }
     for (int t = 0; t < NTA; t++) {
-        const bool sact = t < side * nstrips && t < NTS;
+        const bool sact = t < side * nstrips;
         const int dx = sact ? t % side : 0, dy0 = sact ? (t / side) * NPK : 0;
         for (int k = 0; k < NPK; k++) {
             const int dy = dy0 + k;
@@ -1024,9 +993,6 @@ static int claim_entry(jmh_ctx *c, int *out) {
     return JMH_OK;
 }
 
-extern "C" {
-
-}  // extern "C"
 static int set_reference_any(jmh_ctx *c, int list, int ref_idx, const void *y, const void *u, const void *v, int sy, int sc, bool wide) {
     if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
     if (list != 0 || ref_idx != 0) return JMH_E_UNSUPPORTED_CFG;
@@ -1155,6 +1121,139 @@ static int load_frame_any(jmh_ctx *c, int slot, const void *y, const void *u, co
     HCHK(hipStreamSynchronize(c->st));
     if (!pack_planes(c->h_stage_ref, c->W, c->H, y, u, v, sy, sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
     HCHK(hipMemcpyAsync(c->d_slots + (size_t)slot * c->fsize, c->h_stage_ref, c->fsize, hipMemcpyHostToDevice, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+
+// ---- the unit seams, one helper each for both sample widths (pel = uint8_t: the 8-bit entries,
+//      uint16_t: the High 10 ..._u16 ones, which range-check their samples on the host) ----------
+// SetupFastFullPelSearch's SAD table.  8 bits: slot 0 against the current reference, after the
+// pictures in flight; 16 bits: the search pictures (jmh_search_pictures_u16), centres within +-SR
+template <class pel>
+static int sad_table(jmh_ctx *c, int n_mb, const int32_t *mb_xy, const int32_t *centres, uint16_t *out) {
+    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
+    if (!c || n_mb <= 0 || !mb_xy || !centres || !out) return JMH_E_INVALID_ARG;
+    for (int i = 0; i < n_mb; i++)
+        if (mb_xy[2 * i] < 0 || mb_xy[2 * i] >= c->mbw || mb_xy[2 * i + 1] < 0 || mb_xy[2 * i + 1] >= c->mbh ||
+            (wi && (abs(centres[2 * i]) > c->sr || abs(centres[2 * i + 1]) > c->sr))) return JMH_E_INVALID_ARG;
+    const pel *org, *ref;
+    if constexpr (wi) {
+        if (!c->spic[wi].cur) return JMH_E_STATE;
+        HCHK(hipSetDevice(c->dev));
+        org = (const pel *)c->spic[wi].cur; ref = (const pel *)c->spic[wi].ref;
+    } else {
+        if (c->ref_kind == REF_NONE) return JMH_E_STATE;
+        if (c->bd > 8) return JMH_E_UNSUPPORTED_CFG;   // the 8-bit SAD-table seam (High 10: jmh_ffs_sad_table_u16)
+        HCHK(hipSetDevice(c->dev));
+        int r = drain(c);
+        if (r) return r;
+        org = c->d_slots; ref = ref_ptr(c);
+    }
+    int32_t *d_xy = nullptr, *d_c = nullptr;
+    uint16_t *d_out = nullptr;
+    const size_t on = (size_t)n_mb * 16 * c->npos;
+    DevTemps tmp;
+    HCHK(tmp.alloc(&d_xy, n_mb * 8));
+    HCHK(tmp.alloc(&d_c, n_mb * 8));
+    HCHK(tmp.alloc(&d_out, on * 2));
+    HCHK(hipMemcpyAsync(d_xy, mb_xy, n_mb * 8, hipMemcpyHostToDevice, c->st));
+    HCHK(hipMemcpyAsync(d_c, centres, n_mb * 8, hipMemcpyHostToDevice, c->st));
+    HCHK(jmh_launch_sad_table(org, ref, c->W, c->H, c->sr, n_mb, d_xy, d_c, d_out, c->st));
+    HCHK(hipMemcpyAsync(out, d_out, on * 2, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+
+// dct_luma / dct_luma8x8 at bit_depth (EL = 16 or 64 samples per block)
+template <int EL, class pel>
+static int tq_batch(jmh_ctx *c, int n, const int16_t *resid, const pel *pred, int qp, int intra, int bit_depth, int16_t *levels, pel *recon,
+                    int32_t *coeff_cost, int32_t *nonzero) {
+    if (!c || n <= 0 || !resid || !pred || !levels || !recon || !coeff_cost || !nonzero || qp < 0 || qp > 51 || bit_depth < 8 ||
+        bit_depth > 10) return JMH_E_INVALID_ARG;
+    const int maxv = (1 << bit_depth) - 1;
+    if constexpr (sizeof(pel) == 2)
+        for (size_t k = 0; k < (size_t)n * EL; k++)   // the int32 headroom of the quantiser assumes these ranges
+            if (pred[k] > maxv || resid[k] > maxv || resid[k] < -maxv) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    int16_t *dr, *dl;
+    pel *dp, *drec;
+    int32_t *dcc, *dnz;
+    const size_t cb = (size_t)n * EL * 2, sb = (size_t)n * EL * sizeof(pel);   // bytes of the coefficients, of the samples
+    DevTemps tmp;
+    HCHK(tmp.alloc(&dr, cb)); HCHK(tmp.alloc(&dl, cb));
+    HCHK(tmp.alloc(&dp, sb)); HCHK(tmp.alloc(&drec, sb));
+    HCHK(tmp.alloc(&dcc, (size_t)n * 4)); HCHK(tmp.alloc(&dnz, (size_t)n * 4));
+    HCHK(hipMemcpyAsync(dr, resid, cb, hipMemcpyHostToDevice, c->st));
+    HCHK(hipMemcpyAsync(dp, pred, sb, hipMemcpyHostToDevice, c->st));
+    const int qpb = qp + 6 * (bit_depth - 8), qsel = q_selector(c->cfg, intra != 0);
+    if (EL == 16) HCHK(jmh_launch_tq4x4(n, dr, dp, qpb, qsel, maxv, dl, drec, dcc, dnz, c->st));
+    else HCHK(jmh_launch_tq8x8(n, dr, dp, qpb, qsel, maxv, dl, drec, dcc, dnz, c->st));
+    HCHK(hipMemcpyAsync(levels, dl, cb, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipMemcpyAsync(recon, drec, sb, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipMemcpyAsync(coeff_cost, dcc, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipMemcpyAsync(nonzero, dnz, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+
+// the luma pictures of the per-block searches (the 16-bit ones record their bit depth)
+template <class pel>
+static int search_pictures(jmh_ctx *c, const pel *cur_y, const pel *ref_y, int sy, int bit_depth) {
+    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
+    if (!c || !cur_y || !ref_y || sy < c->W || bit_depth < 8 || bit_depth > 10) return JMH_E_INVALID_ARG;
+    if constexpr (wi) {
+        const int maxv = (1 << bit_depth) - 1;
+        for (int y = 0; y < c->H; y++)   // out-of-range samples would break the 19-bit cost keys
+            for (int x = 0; x < c->W; x++)
+                if (cur_y[(size_t)y * sy + x] > maxv || ref_y[(size_t)y * sy + x] > maxv) return JMH_E_INVALID_ARG;
+    }
+    HCHK(hipSetDevice(c->dev));
+    auto &sp = c->spic[wi];
+    const size_t row = (size_t)c->W * sizeof(pel);
+    if (!sp.cur) {
+        if (hipMalloc(&sp.cur, row * c->H) != hipSuccess) return JMH_E_OOM;
+        if (hipMalloc(&sp.ref, row * c->H) != hipSuccess) { (void)hipFree(sp.cur); sp.cur = nullptr; return JMH_E_OOM; }
+    }
+    HCHK(hipStreamSynchronize(c->st));   // an earlier search may still read the buffers
+    HCHK(hipMemcpy2DAsync(sp.cur, row, cur_y, (size_t)sy * sizeof(pel), row, c->H, hipMemcpyHostToDevice, c->st));
+    HCHK(hipMemcpy2DAsync(sp.ref, row, ref_y, (size_t)sy * sizeof(pel), row, c->H, hipMemcpyHostToDevice, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    if (wi) c->hbd_bits = bit_depth;
+    return JMH_OK;
+}
+
+static int check_block_requests(const jmh_ctx *c, int n, const jmh_block_search *req) {
+    for (int i = 0; i < n; i++) {   // the kernel's block and window assumptions, checked on the host
+        const jmh_block_search &q = req[i];
+        if (q.blocktype < 1 || q.blocktype > 7 || q.mb_x < 0 || q.mb_x >= c->mbw || q.mb_y < 0 || q.mb_y >= c->mbh) return JMH_E_INVALID_ARG;
+        static const int bw4[8] = {4, 4, 4, 2, 2, 2, 1, 1}, bh4[8] = {4, 4, 2, 4, 2, 1, 2, 1};
+        if (q.block_x < 0 || q.block_y < 0 || q.block_x + bw4[q.blocktype] > 4 || q.block_y + bh4[q.blocktype] > 4) return JMH_E_INVALID_ARG;
+        if (q.search_range < 0 || q.search_range > c->sr) return JMH_E_INVALID_ARG;
+        if (q.search_range > SRMAX) return JMH_E_UNSUPPORTED_CFG;   // 13-bit spiral order keys: (2 SR + 1)^2 < 8192
+        if (q.lambda_factor < 0 || q.lambda_factor > (1 << 24)) return JMH_E_INVALID_ARG;
+        if (q.search_mode != 0 && q.search_mode != -1) return JMH_E_UNSUPPORTED_CFG;
+        if (abs(q.centre[0]) > 2048 || abs(q.centre[1]) > 2048 || abs(q.pred_mv[0]) > 8192 || abs(q.pred_mv[1]) > 8192) return JMH_E_INVALID_ARG;
+    }
+    return JMH_OK;
+}
+// BlockMotionSearch per request on the search pictures of pel's width; maxv = 2^(their bit depth) - 1
+template <class pel>
+static int block_motion_search(jmh_ctx *c, int n, const jmh_block_search *req, jmh_block_result *res, int maxv) {
+    if (!c || n <= 0 || !req || !res) return JMH_E_INVALID_ARG;
+    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
+    const auto &sp = c->spic[wi];
+    if (!sp.cur) return JMH_E_STATE;
+    int r = check_block_requests(c, n, req);
+    if (r) return r;
+    HCHK(hipSetDevice(c->dev));
+    DevTemps tmp;
+    jmh_block_search *d_req;
+    jmh_block_result *d_res;
+    HCHK(tmp.alloc(&d_req, (size_t)n * sizeof(jmh_block_search)));
+    HCHK(tmp.alloc(&d_res, (size_t)n * sizeof(jmh_block_result)));
+    HCHK(hipMemcpyAsync(d_req, req, (size_t)n * sizeof(jmh_block_search), hipMemcpyHostToDevice, c->st));
+    HCHK(jmh_launch_block_search(n, d_req, d_res, (const pel *)sp.cur, (const pel *)sp.ref, c->W, c->H, c->cfg.use_hadamard, maxv, c->st));
+    HCHK(hipMemcpyAsync(res, d_res, (size_t)n * sizeof(jmh_block_result), hipMemcpyDeviceToHost, c->st));
     HCHK(hipStreamSynchronize(c->st));
     return JMH_OK;
 }
@@ -1293,215 +1392,38 @@ int jmh_get_timing(jmh_ctx *c, jmh_timing *t) {
 }
 
 int jmh_ffs_sad_table(jmh_ctx *c, int n_mb, const int32_t *mb_xy, const int32_t *centres, uint16_t *out) {
-    if (!c || n_mb <= 0 || !mb_xy || !centres || !out) return JMH_E_INVALID_ARG;
-    for (int i = 0; i < n_mb; i++)
-        if (mb_xy[2 * i] < 0 || mb_xy[2 * i] >= c->mbw || mb_xy[2 * i + 1] < 0 || mb_xy[2 * i + 1] >= c->mbh) return JMH_E_INVALID_ARG;
-    if (c->ref_kind == REF_NONE) return JMH_E_STATE;
-    if (c->bd > 8) return JMH_E_UNSUPPORTED_CFG;   // the 8-bit SAD-table seam (High 10: jmh_ffs_sad_table_u16)
-    HCHK(hipSetDevice(c->dev));
-    int r = drain(c);
-    if (r) return r;
-    int32_t *d_xy = nullptr, *d_c = nullptr;
-    uint16_t *d_out = nullptr;
-    size_t on = (size_t)n_mb * 16 * c->npos;
-    DevTemps tmp;
-    HCHK(tmp.alloc(&d_xy, n_mb * 8));
-    HCHK(tmp.alloc(&d_c, n_mb * 8));
-    HCHK(tmp.alloc(&d_out, on * 2));
-    HCHK(hipMemcpyAsync(d_xy, mb_xy, n_mb * 8, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpyAsync(d_c, centres, n_mb * 8, hipMemcpyHostToDevice, c->st));
-    HCHK(jmh_launch_sad_table(c->d_slots, ref_ptr(c), c->W, c->H, c->sr, n_mb, d_xy, d_c, d_out, c->st));
-    HCHK(hipMemcpyAsync(out, d_out, on * 2, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
+    return sad_table<uint8_t>(c, n_mb, mb_xy, centres, out);
 }
-
 int jmh_tq4x4_batch(jmh_ctx *c, int n, const int16_t *resid, const uint8_t *pred, int qp, int intra, int16_t *levels,
                     uint8_t *recon, int32_t *coeff_cost, int32_t *nonzero) {
-    if (!c || n <= 0 || !resid || !pred || !levels || !recon || !coeff_cost || !nonzero || qp < 0 || qp > 51) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    int16_t *dr, *dl;
-    uint8_t *dp, *drec;
-    int32_t *dcc, *dnz;
-    DevTemps tmp;
-    HCHK(tmp.alloc(&dr, (size_t)n * 32)); HCHK(tmp.alloc(&dl, (size_t)n * 32));
-    HCHK(tmp.alloc(&dp, (size_t)n * 16)); HCHK(tmp.alloc(&drec, (size_t)n * 16));
-    HCHK(tmp.alloc(&dcc, (size_t)n * 4)); HCHK(tmp.alloc(&dnz, (size_t)n * 4));
-    HCHK(hipMemcpyAsync(dr, resid, n * 32, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpyAsync(dp, pred, n * 16, hipMemcpyHostToDevice, c->st));
-    HCHK(jmh_launch_tq4x4(n, dr, dp, qp, q_selector(c->cfg, intra != 0), dl, drec, dcc, dnz, c->st));
-    HCHK(hipMemcpyAsync(levels, dl, n * 32, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(recon, drec, n * 16, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(coeff_cost, dcc, n * 4, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(nonzero, dnz, n * 4, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
+    return tq_batch<16>(c, n, resid, pred, qp, intra, 8, levels, recon, coeff_cost, nonzero);
 }
-
 int jmh_tq8x8_batch(jmh_ctx *c, int n, const int16_t *resid, const uint8_t *pred, int qp, int intra, int16_t *levels,
                     uint8_t *recon, int32_t *coeff_cost, int32_t *nonzero) {
-    if (!c || n <= 0 || !resid || !pred || !levels || !recon || !coeff_cost || !nonzero || qp < 0 || qp > 51) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    int16_t *dr, *dl;
-    uint8_t *dp, *drec;
-    int32_t *dcc, *dnz;
-    DevTemps tmp;
-    HCHK(tmp.alloc(&dr, (size_t)n * 128)); HCHK(tmp.alloc(&dl, (size_t)n * 128));
-    HCHK(tmp.alloc(&dp, (size_t)n * 64)); HCHK(tmp.alloc(&drec, (size_t)n * 64));
-    HCHK(tmp.alloc(&dcc, (size_t)n * 4)); HCHK(tmp.alloc(&dnz, (size_t)n * 4));
-    HCHK(hipMemcpyAsync(dr, resid, n * 128, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpyAsync(dp, pred, n * 64, hipMemcpyHostToDevice, c->st));
-    HCHK(jmh_launch_tq8x8(n, dr, dp, qp, q_selector(c->cfg, intra != 0), dl, drec, dcc, dnz, c->st));
-    HCHK(hipMemcpyAsync(levels, dl, n * 128, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(recon, drec, n * 64, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(coeff_cost, dcc, n * 4, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(nonzero, dnz, n * 4, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
+    return tq_batch<64>(c, n, resid, pred, qp, intra, 8, levels, recon, coeff_cost, nonzero);
 }
-
-int jmh_search_pictures(jmh_ctx *c, const uint8_t *cur_y, const uint8_t *ref_y, int sy) {
-    if (!c || !cur_y || !ref_y || sy < c->W) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    const size_t ls = (size_t)c->W * c->H;
-    if (!c->d_scur) {
-        if (hipMalloc((void **)&c->d_scur, ls) != hipSuccess) return JMH_E_OOM;
-        if (hipMalloc((void **)&c->d_sref, ls) != hipSuccess) { (void)hipFree(c->d_scur); c->d_scur = nullptr; return JMH_E_OOM; }
-    }
-    HCHK(hipStreamSynchronize(c->st));   // an earlier search may still read the buffers
-    HCHK(hipMemcpy2DAsync(c->d_scur, c->W, cur_y, sy, c->W, c->H, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpy2DAsync(c->d_sref, c->W, ref_y, sy, c->W, c->H, hipMemcpyHostToDevice, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
-}
-
-static int check_block_requests(const jmh_ctx *c, int n, const jmh_block_search *req) {
-    for (int i = 0; i < n; i++) {   // the kernel's block and window assumptions, checked on the host
-        const jmh_block_search &q = req[i];
-        if (q.blocktype < 1 || q.blocktype > 7 || q.mb_x < 0 || q.mb_x >= c->mbw || q.mb_y < 0 || q.mb_y >= c->mbh) return JMH_E_INVALID_ARG;
-        static const int bw4[8] = {4, 4, 4, 2, 2, 2, 1, 1}, bh4[8] = {4, 4, 2, 4, 2, 1, 2, 1};
-        if (q.block_x < 0 || q.block_y < 0 || q.block_x + bw4[q.blocktype] > 4 || q.block_y + bh4[q.blocktype] > 4) return JMH_E_INVALID_ARG;
-        if (q.search_range < 0 || q.search_range > c->sr) return JMH_E_INVALID_ARG;
-        if (q.search_range > SRMAX) return JMH_E_UNSUPPORTED_CFG;   // 13-bit spiral order keys: (2 SR + 1)^2 < 8192
-        if (q.lambda_factor < 0 || q.lambda_factor > (1 << 24)) return JMH_E_INVALID_ARG;
-        if (q.search_mode != 0 && q.search_mode != -1) return JMH_E_UNSUPPORTED_CFG;
-        if (abs(q.centre[0]) > 2048 || abs(q.centre[1]) > 2048 || abs(q.pred_mv[0]) > 8192 || abs(q.pred_mv[1]) > 8192) return JMH_E_INVALID_ARG;
-    }
-    return JMH_OK;
-}
+int jmh_search_pictures(jmh_ctx *c, const uint8_t *cur_y, const uint8_t *ref_y, int sy) { return search_pictures(c, cur_y, ref_y, sy, 8); }
 int jmh_block_motion_search(jmh_ctx *c, int n, const jmh_block_search *req, jmh_block_result *res) {
-    if (!c || n <= 0 || !req || !res) return JMH_E_INVALID_ARG;
-    if (!c->d_scur) return JMH_E_STATE;
-    int r = check_block_requests(c, n, req);
-    if (r) return r;
-    HCHK(hipSetDevice(c->dev));
-    DevTemps tmp;
-    jmh_block_search *d_req;
-    jmh_block_result *d_res;
-    HCHK(tmp.alloc(&d_req, (size_t)n * sizeof(jmh_block_search)));
-    HCHK(tmp.alloc(&d_res, (size_t)n * sizeof(jmh_block_result)));
-    HCHK(hipMemcpyAsync(d_req, req, (size_t)n * sizeof(jmh_block_search), hipMemcpyHostToDevice, c->st));
-    HCHK(jmh_launch_block_search(n, d_req, d_res, c->d_scur, c->d_sref, c->W, c->H, c->cfg.use_hadamard, c->st));
-    HCHK(hipMemcpyAsync(res, d_res, (size_t)n * sizeof(jmh_block_result), hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
+    return block_motion_search<uint8_t>(c, n, req, res, 255);
 }
 
 // ---- High 10 seams (16-bit samples) ----------------------------------------------------------
 int jmh_search_pictures_u16(jmh_ctx *c, const uint16_t *cur_y, const uint16_t *ref_y, int sy, int bit_depth) {
-    if (!c || !cur_y || !ref_y || sy < c->W || bit_depth < 8 || bit_depth > 10) return JMH_E_INVALID_ARG;
-    const int maxv = (1 << bit_depth) - 1;
-    for (int y = 0; y < c->H; y++)   // out-of-range samples would break the 19-bit cost keys
-        for (int x = 0; x < c->W; x++)
-            if (cur_y[(size_t)y * sy + x] > maxv || ref_y[(size_t)y * sy + x] > maxv) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    const size_t ls = (size_t)c->W * c->H * 2;
-    if (!c->d_scur16) {
-        if (hipMalloc((void **)&c->d_scur16, ls) != hipSuccess) return JMH_E_OOM;
-        if (hipMalloc((void **)&c->d_sref16, ls) != hipSuccess) { (void)hipFree(c->d_scur16); c->d_scur16 = nullptr; return JMH_E_OOM; }
-    }
-    HCHK(hipStreamSynchronize(c->st));   // an earlier search may still read the buffers
-    HCHK(hipMemcpy2DAsync(c->d_scur16, (size_t)c->W * 2, cur_y, (size_t)sy * 2, (size_t)c->W * 2, c->H, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpy2DAsync(c->d_sref16, (size_t)c->W * 2, ref_y, (size_t)sy * 2, (size_t)c->W * 2, c->H, hipMemcpyHostToDevice, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    c->hbd_bits = bit_depth;
-    return JMH_OK;
+    return search_pictures(c, cur_y, ref_y, sy, bit_depth);
 }
 int jmh_block_motion_search_u16(jmh_ctx *c, int n, const jmh_block_search *req, jmh_block_result *res) {
-    if (!c || n <= 0 || !req || !res) return JMH_E_INVALID_ARG;
-    if (!c->d_scur16) return JMH_E_STATE;
-    int r = check_block_requests(c, n, req);
-    if (r) return r;
-    HCHK(hipSetDevice(c->dev));
-    DevTemps tmp;
-    jmh_block_search *d_req;
-    jmh_block_result *d_res;
-    HCHK(tmp.alloc(&d_req, (size_t)n * sizeof(jmh_block_search)));
-    HCHK(tmp.alloc(&d_res, (size_t)n * sizeof(jmh_block_result)));
-    HCHK(hipMemcpyAsync(d_req, req, (size_t)n * sizeof(jmh_block_search), hipMemcpyHostToDevice, c->st));
-    HCHK(jmh_launch_block_search_u16(n, d_req, d_res, c->d_scur16, c->d_sref16, c->W, c->H, c->cfg.use_hadamard, c->hbd_bits, c->st));
-    HCHK(hipMemcpyAsync(res, d_res, (size_t)n * sizeof(jmh_block_result), hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
+    return block_motion_search<uint16_t>(c, n, req, res, c ? (1 << c->hbd_bits) - 1 : 0);
 }
 int jmh_ffs_sad_table_u16(jmh_ctx *c, int n_mb, const int32_t *mb_xy, const int32_t *centres, uint16_t *out) {
-    if (!c || n_mb <= 0 || !mb_xy || !centres || !out) return JMH_E_INVALID_ARG;
-    for (int i = 0; i < n_mb; i++)
-        if (mb_xy[2 * i] < 0 || mb_xy[2 * i] >= c->mbw || mb_xy[2 * i + 1] < 0 || mb_xy[2 * i + 1] >= c->mbh ||
-            abs(centres[2 * i]) > c->sr || abs(centres[2 * i + 1]) > c->sr) return JMH_E_INVALID_ARG;
-    if (!c->d_scur16) return JMH_E_STATE;
-    HCHK(hipSetDevice(c->dev));
-    int32_t *d_xy = nullptr, *d_c = nullptr;
-    uint16_t *d_out = nullptr;
-    const size_t on = (size_t)n_mb * 16 * c->npos;
-    DevTemps tmp;
-    HCHK(tmp.alloc(&d_xy, n_mb * 8));
-    HCHK(tmp.alloc(&d_c, n_mb * 8));
-    HCHK(tmp.alloc(&d_out, on * 2));
-    HCHK(hipMemcpyAsync(d_xy, mb_xy, n_mb * 8, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpyAsync(d_c, centres, n_mb * 8, hipMemcpyHostToDevice, c->st));
-    HCHK(jmh_launch_sad_table_u16(c->d_scur16, c->d_sref16, c->W, c->H, c->sr, n_mb, d_xy, d_c, d_out, c->st));
-    HCHK(hipMemcpyAsync(out, d_out, on * 2, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
+    return sad_table<uint16_t>(c, n_mb, mb_xy, centres, out);
 }
-}  // extern "C"
-// dct_luma / dct_luma8x8 at bit_depth (EL = 16 or 64 samples per block)
-template <int EL>
-static int tq_batch_u16(jmh_ctx *c, int n, const int16_t *resid, const uint16_t *pred, int qp, int intra, int bit_depth, int16_t *levels,
-                        uint16_t *recon, int32_t *coeff_cost, int32_t *nonzero) {
-    if (!c || n <= 0 || !resid || !pred || !levels || !recon || !coeff_cost || !nonzero || qp < 0 || qp > 51 || bit_depth < 8 ||
-        bit_depth > 10) return JMH_E_INVALID_ARG;
-    const int maxv = (1 << bit_depth) - 1;
-    for (size_t k = 0; k < (size_t)n * EL; k++)   // the int32 headroom of the quantiser assumes these ranges
-        if (pred[k] > maxv || resid[k] > maxv || resid[k] < -maxv) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    int16_t *dr, *dl;
-    uint16_t *dp, *drec;
-    int32_t *dcc, *dnz;
-    DevTemps tmp;
-    HCHK(tmp.alloc(&dr, (size_t)n * EL * 2)); HCHK(tmp.alloc(&dl, (size_t)n * EL * 2));
-    HCHK(tmp.alloc(&dp, (size_t)n * EL * 2)); HCHK(tmp.alloc(&drec, (size_t)n * EL * 2));
-    HCHK(tmp.alloc(&dcc, (size_t)n * 4)); HCHK(tmp.alloc(&dnz, (size_t)n * 4));
-    HCHK(hipMemcpyAsync(dr, resid, (size_t)n * EL * 2, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpyAsync(dp, pred, (size_t)n * EL * 2, hipMemcpyHostToDevice, c->st));
-    if (EL == 16) HCHK(jmh_launch_tq4x4_u16(n, dr, dp, qp, q_selector(c->cfg, intra != 0), bit_depth, dl, drec, dcc, dnz, c->st));
-    else HCHK(jmh_launch_tq8x8_u16(n, dr, dp, qp, q_selector(c->cfg, intra != 0), bit_depth, dl, drec, dcc, dnz, c->st));
-    HCHK(hipMemcpyAsync(levels, dl, (size_t)n * EL * 2, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(recon, drec, (size_t)n * EL * 2, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(coeff_cost, dcc, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(nonzero, dnz, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
-}
-extern "C" {
 int jmh_tq4x4_batch_u16(jmh_ctx *c, int n, const int16_t *resid, const uint16_t *pred, int qp, int intra, int bit_depth, int16_t *levels,
                         uint16_t *recon, int32_t *coeff_cost, int32_t *nonzero) {
-    return tq_batch_u16<16>(c, n, resid, pred, qp, intra, bit_depth, levels, recon, coeff_cost, nonzero);
+    return tq_batch<16>(c, n, resid, pred, qp, intra, bit_depth, levels, recon, coeff_cost, nonzero);
 }
 int jmh_tq8x8_batch_u16(jmh_ctx *c, int n, const int16_t *resid, const uint16_t *pred, int qp, int intra, int bit_depth, int16_t *levels,
                         uint16_t *recon, int32_t *coeff_cost, int32_t *nonzero) {
-    return tq_batch_u16<64>(c, n, resid, pred, qp, intra, bit_depth, levels, recon, coeff_cost, nonzero);
+    return tq_batch<64>(c, n, resid, pred, qp, intra, bit_depth, levels, recon, coeff_cost, nonzero);
 }
 
 /* test seam: quarter-pel planes of the current reference, [16][H+8][W+8] (UnifiedOneForthPix) */

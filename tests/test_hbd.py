@@ -204,7 +204,7 @@ def test_gpu_hbd_block_motion_search(w, h, sr, had, bd):
 @pytest.mark.gpu
 def test_gpu_hbd_extremes_and_sad_table():
     """Saturated 0 / 1023 pictures (the 6-tap overshoots both ways) through the per-block search
-    and the SAD table (v_sad_u16)."""
+    and the SAD table."""
     w, h, sr = 96, 64, 8
     cur, ref = extreme_pic(w, h, 11), extreme_pic(w, h, 12)
     g = jmhip.Encoder(w, h, search_range=sr)
@@ -228,11 +228,33 @@ def test_gpu_hbd_extremes_and_sad_table():
 def test_gpu_hbd_at_8_bits_equals_8bit_seams():
     """The 16-bit seams at bit depth 8 give exactly the 8-bit seams' results on the device."""
     w, h, sr = 176, 144, 16
-    pics = [jmhip.synth_frame(w, h, 4, i)[0] for i in range(2)]
+    frames = [jmhip.synth_frame(w, h, 4, i) for i in range(2)]
+    pics = [f[0] for f in frames]
     g = jmhip.Encoder(w, h, search_range=sr)
     g.search_pictures(pics[1], pics[0])
     g.search_pictures_u16(pics[1].astype(np.uint16), pics[0].astype(np.uint16), 8)
     reqs = block_requests(w, h, sr, 150, 9)
     for a, b in zip(g.block_motion_search(reqs), g.block_motion_search_u16(reqs)):
         assert bytes(a) == bytes(b)
+    # the SAD table of every macroblock: slot 0 against the reference (8-bit seam) == the 16-bit
+    # search pictures loaded above, random centres within +-SR
+    g.load_frame(0, *frames[1])
+    g.set_reference(*frames[0])
+    mbxy = np.array([[x, y] for y in range(h // 16) for x in range(w // 16)], np.int32)
+    cen = np.random.default_rng(17).integers(-sr, sr + 1, mbxy.shape).astype(np.int32)
+    assert np.array_equal(g.sad_table(mbxy, cen), g.sad_table_u16(mbxy, cen))
+    # dct_luma / dct_luma8x8: 96 blocks each with test_gpu_hbd_tq_all_qp's extreme rows (+-255, 0)
+    rng = np.random.default_rng(48)
+    for el, f8 in ((16, g.tq4x4), (64, g.tq8x8)):
+        resid = rng.integers(-255, 256, (96, el)).astype(np.int16)
+        resid[:16] = np.where(rng.random((16, el)) < 0.5, 255, -255)
+        resid[16:20] = 0
+        pred = rng.integers(0, 256, (96, el)).astype(np.uint8)
+        pred[:8] = np.where(rng.random((8, el)) < 0.5, 255, 0)
+        for qp in (0, 23, 51):
+            for intra in (0, 1):
+                a = f8(resid, pred, qp, intra)
+                b = g.tq_u16(resid, pred.astype(np.uint16), qp, intra, 8)
+                for x, y in zip(a, b):
+                    assert np.array_equal(np.asarray(x, np.int64), np.asarray(y, np.int64)), (el, qp, intra)
     g.close()

@@ -11,7 +11,6 @@
 #   smoke   __graft_entry__.smoke()                  -> gpurun_out/TAG_smoke.log
 #   bench   bench.py --full (defaults, with CPU baseline and host path) -> $OUT/TAG_bench.json
 #   bench20 bench.py --steps 20 --warmup 5 (the driver's invocation, no CPU baseline)
-#   benchf8 bench20 with JMH_FINAL_OCC8=1 (k_mb_final's 8-per-CU build for every tick: A/B)
 #   c3      bench.py --config 3 --full (with CPU baseline) -> $OUT/TAG_c3_bench.json
 #   c3s     config 3 with SliceMode 1, SliceArgument 240 (config 5's one-row slices, 8-bit, CAVLC)
 #   c5      bench.py --config 5 --full (High 10, RDO on, 240-MB slices; with CPU baseline)
@@ -63,8 +62,6 @@ for s in "$@"; do
             cat $OUT/${TAG}_bench.json ;;
     bench20) run bench20 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_bench20.json || exit $?
             cat gpurun_out/${TAG}_bench20.json ;;
-    benchf8) JMH_FINAL_OCC8=1 run benchf8 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_benchf8.json || exit $?
-            cat gpurun_out/${TAG}_benchf8.json ;;
     c3)     run c3 900 python bench.py --full --config 3 > $OUT/${TAG}_c3_bench.json 2> $OUT/${TAG}_c3_bench.err || exit $?
             cat $OUT/${TAG}_c3_bench.json ;;
     c5)     run c5 1100 python bench.py --full --config 5 > $OUT/${TAG}_c5_bench.json 2> $OUT/${TAG}_c5_bench.err || exit $?

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(NTA, 4) void k_subpel_bench(DevParams d, const uint
     for (int i = tid; i < 8 * 16 * 2; i += NTA) (&s.all_mv[0][0][0])[i] = (int16_t)(p[i] % 7 - 3);
     if (tid < 32) (&s.motion_cost[0][0])[tid] = 0;
     // full-pel winners: spiral order 1 + (b % 60) around the window centre
-    if (tid < (NTS / 64) * MAXNS) (&s.red[0][0])[tid] = (100u << 13) | (unsigned)(1 + (b + tid) % 60);
+    if (tid < (NTA / 64) * MAXNS) (&s.red[0][0])[tid] = (100u << 13) | (unsigned)(1 + (b + tid) % 60);
     __syncthreads();
     unsigned long long t0 = 0, t1 = 0;
     const SDesc q4 = {7, 1, 0, 0, 7, 0, 1, 0}, q8 = {4, 0, 0, 0, 0, 0, 0, 0};
