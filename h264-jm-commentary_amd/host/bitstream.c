@@ -427,6 +427,7 @@ static void write_slice_header(jm_bits *b, const jm_seq *s, const jm_slice *sl) 
         if (s->lf_disable != 1) { jm_put_se(b, s->lf_alpha); jm_put_se(b, s->lf_beta); }
     }
 }
+void jm_write_slice_header(jm_bits *b, const jm_seq *s, const jm_slice *sl) { write_slice_header(b, s, sl); }
 
 jm_slice_writer *jm_slice_begin(jm_bits *b, const jm_seq *s, const jm_slice *sl) {
     jm_slice_writer *sw = calloc(1, sizeof(*sw));

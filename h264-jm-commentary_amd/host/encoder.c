@@ -126,6 +126,75 @@ static int encode_picture_slices(jm86_img *im, const jm_seq *s, const jm_slice *
     return JMH_OK;
 }
 
+/* ---- DeviceCAVLC 1: image.c › code_a_picture [J] with the slice data written on the device ------
+ * The slice headers are written here (jm_write_slice_header); the bits of each header's last,
+ * partial byte go to the device with the slice's macroblock range, and the device returns
+ * slice_data() + rbsp_trailing_bits behind them (jmh_cavlc_write_slices).  Header bytes + device
+ * bytes are the slice's RBSP, wrapped by jm_write_nal as ever.  No jm_slice_write_mb, no rate
+ * cross-check. */
+static jm_cavlc_slices_fn device_cavlc_fn;
+void jm_set_device_cavlc(jm_cavlc_slices_fn fn) { device_cavlc_fn = fn; }
+
+typedef struct dcavlc {
+    int n;                       /* slices per picture */
+    jmh_slice_desc *d;
+    jmh_slice_bytes *where;
+    jm_bits *hdr;                /* per slice: the header, then the whole RBSP */
+    uint8_t *buf;
+    size_t cap;
+} dcavlc_t;
+
+static void dcavlc_free(dcavlc_t *dc) {
+    if (dc->hdr) for (int i = 0; i < dc->n; i++) jm_bits_free(&dc->hdr[i]);
+    free(dc->d); free(dc->where); free(dc->hdr); free(dc->buf);
+    memset(dc, 0, sizeof(*dc));
+}
+static int dcavlc_init(dcavlc_t *dc, const jm_seq *s) {
+    const int nmb = s->mbw * s->mbh, step = s->slice_mbs > 0 ? s->slice_mbs : nmb;
+    memset(dc, 0, sizeof(*dc));
+    dc->n = (nmb + step - 1) / step;
+    dc->d = (jmh_slice_desc *)calloc(dc->n, sizeof(*dc->d));
+    dc->where = (jmh_slice_bytes *)calloc(dc->n, sizeof(*dc->where));
+    dc->hdr = (jm_bits *)calloc(dc->n, sizeof(*dc->hdr));
+    dc->cap = (size_t)nmb * 64 + 1024;
+    dc->buf = (uint8_t *)malloc(dc->cap);
+    if (!dc->d || !dc->where || !dc->hdr || !dc->buf) { dcavlc_free(dc); return JMH_E_OOM; }
+    return JMH_OK;
+}
+static int device_picture_slices(dcavlc_t *dc, jm_backend *be, const jm_seq *s, const jm_slice *sl0, jm_bits *out) {
+    const int nmb = s->mbw * s->mbh, step = s->slice_mbs > 0 ? s->slice_mbs : nmb;
+    for (int i = 0; i < dc->n; i++) {
+        jm_slice sl = *sl0;
+        sl.first_mb = i * step;
+        jm_bits *h = &dc->hdr[i];
+        h->len = 0; h->acc = 0; h->nacc = 0;
+        jm_write_slice_header(h, s, &sl);
+        dc->d[i].first_mb = sl.first_mb;
+        dc->d[i].n_mb = sl.first_mb + step < nmb ? step : nmb - sl.first_mb;
+        dc->d[i].slice_type = sl0->slice_type;
+        dc->d[i].lead_nbits = h->nacc;
+        dc->d[i].lead_bits = (uint32_t)h->acc;
+    }
+    memset(dc->where, 0, dc->n * sizeof(*dc->where));
+    int r = device_cavlc_fn(be->ctx, dc->n, dc->d, dc->buf, dc->cap, dc->where);
+    const size_t total = (size_t)(dc->where[dc->n - 1].offset + dc->where[dc->n - 1].nbytes);
+    if (r == JMH_E_INVALID_ARG && total > dc->cap) {   /* the counted size: grow and write again */
+        uint8_t *nb = (uint8_t *)realloc(dc->buf, 2 * total);
+        if (!nb) return JMH_E_OOM;
+        dc->buf = nb; dc->cap = 2 * total;
+        r = device_cavlc_fn(be->ctx, dc->n, dc->d, dc->buf, dc->cap, dc->where);
+    }
+    if (r) return r;
+    for (int i = 0; i < dc->n; i++) {
+        jm_bits *h = &dc->hdr[i];
+        jm_bits t = {dc->buf + dc->where[i].offset, dc->where[i].nbytes, dc->where[i].nbytes, 0, 0};
+        h->acc = 0; h->nacc = 0;                /* the partial byte comes back as the first device byte */
+        jm_bits_append(h, &t);
+        jm_write_nal(out, sl0->idr ? 3 : 2, sl0->idr ? 5 : 1, h);
+    }
+    return JMH_OK;
+}
+
 /* ---- parallel slice writing (WriterThreads > 0, pipelined device backend) -------------------
  * The slices of different pictures are independent once their macroblock results exist (one
  * slice per picture, device deblocking), so popped pictures are written by a pool of threads,
@@ -224,6 +293,10 @@ static void job_release(wpool_t *P, int k) {
 
 int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *log) {
     memset(st, 0, sizeof(*st));
+    if (inp->device_cavlc && !device_cavlc_fn) {
+        fprintf(stderr, "DeviceCAVLC=1 needs the device backend (backend '%s' writes its slices on the host: DeviceCAVLC=0)\n", be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     jmh_config cfg;
     jm_fill_config(inp, &cfg);
     int W = cfg.width, H = cfg.height;
@@ -261,7 +334,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     const int depth = pipelined ? be->depth : 1;
     /* parallel slice writing: pipelined device backend, not with the call surface's per-MB
        device searches (those share the context with the frame loop) */
-    const int nwr = (pipelined && !inp->jm_call_surface) ? inp->writer_threads : 0;
+    const int nwr = (pipelined && !inp->jm_call_surface && !inp->device_cavlc) ? inp->writer_threads : 0;
     const int nj = nwr ? 2 * nwr : 0;                  /* jobs in flight: queued + running + done */
     const int plen = depth + nj + 1;                   /* source slots: a job's source stays put */
     typedef struct { jm_pic cur; jmh_frame_params fp; int f, is_i, frame_num; } pend_t;
@@ -285,6 +358,8 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     memset(&im, 0, sizeof(im));
     wpool_t pool;
     memset(&pool, 0, sizeof(pool));
+    dcavlc_t dc;
+    memset(&dc, 0, sizeof(dc));
     int st_ret = 0, njobs_init = 0, nstarted = 0, pool_sync = 0;
     long jseq = 0, jflushed = 0;   /* jobs submitted / emitted (picture order) */
     double copy_ms = 0, write_ms = 0;
@@ -292,6 +367,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     jm_bits out, rbsp;
     jm_bits_init(&out); jm_bits_init(&rbsp);
     if (!res || jm86_init(&im, inp, be, W, H)) { st_ret = JMH_E_OOM; goto cleanup; }
+    if (inp->device_cavlc && dcavlc_init(&dc, &s)) { st_ret = JMH_E_OOM; goto cleanup; }
     if (nwr) {
         pool.nj = nj; pool.s = &s; pool.inp = inp; pool.nth = nwr;
         pool.jobs = (wjob_t *)calloc(nj, sizeof(wjob_t));
@@ -322,6 +398,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fprintf(log, "------------------------------- MI355X jm-hot-path lencod (%s) -------------------------------\n", be->name);
         if (pipelined) fprintf(log, " (%d pictures in flight%s)\n", depth, nwr ? ", parallel slice writing" : "");
         if (nwr) fprintf(log, " (%d slice-writer threads)\n", nwr);
+        if (inp->device_cavlc) fprintf(log, " (CAVLC slice data written on the device)\n");
         fprintf(log, " Frame  Bit/pic  QP   SnrY    SnrU    SnrV    Time(ms) MET(ms) Frm/Fld  I D\n");
     }
     double t_start = now_ms();
@@ -382,7 +459,9 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         sl.idr = p_->f == 0; sl.slice_type = p_->fp.slice_type; sl.frame_num = p_->frame_num;      \
         sl.poc_lsb = 2 * p_->f; sl.idr_pic_id = 0; sl.qp = p_->fp.qp;                              \
         sl.first_mb = 0;                                                                           \
-        { int e_ = encode_picture_slices(&im, &s, &sl, &p_->fp, &p_->cur, &rec, &out); if (e_) { st_ret = e_; break; } } \
+        { int e_ = inp->device_cavlc ? device_picture_slices(&dc, be, &s, &sl, &out)                \
+                                     : encode_picture_slices(&im, &s, &sl, &p_->fp, &p_->cur, &rec, &out); \
+          if (e_) { if (inp->device_cavlc) fprintf(stderr, "device CAVLC writer failed: status %d\n", e_); st_ret = e_; break; } } \
         double t2 = now_ms();                                                                      \
         st->entropy_ms += t2 - t1;                                                                 \
         long pic_bits = out.len * 8;                                                               \
@@ -487,6 +566,7 @@ cleanup:
         pthread_cond_destroy(&pool.cv_done);
     }
     free(pool.jobs); free(pool.queue); free(pool.th);
+    dcavlc_free(&dc);
     img = &im;
     st->surface_checked = im.surface_checked;
     st->surface_searches = im.surface_searches;
@@ -510,7 +590,7 @@ cleanup:
                 st->total_ms / 1e3, st->me_tq_ms / 1e3, st->psnr_y, st->psnr_u, st->psnr_v, st->bits);
     if (log && st->frames)
         fprintf(log, " Host per picture: slice writing + PSNR %.2f ms (%s), results + readback (+ host deblocking) %.2f ms, wall %.2f ms\n",
-                st->entropy_ms / st->frames, nwr ? "writer threads" : "main thread", st->deblock_ms / st->frames,
+                st->entropy_ms / st->frames, nwr ? "writer threads" : inp->device_cavlc ? "the device call, no PSNR" : "main thread", st->deblock_ms / st->frames,
                 st->total_ms / st->frames);
     if (log && st->frames)
         fprintf(log, " Main thread per picture: read %.2f ms, push %.2f, pop (wait) %.2f, results to writer %.2f, flush %.2f\n",

@@ -11,6 +11,7 @@
 #ifndef JMHOST_H
 #define JMHOST_H
 
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include "../../include/jmhip.h"
@@ -71,6 +72,9 @@ typedef struct jm_input {
                                   searches through PartitionMotionSearch / BlockMotionSearch
                                   (the per-block device seam), checked against the wavefront
                                   decision (host/jm86.c)                                      */
+    int  device_cavlc;         /* (this build) DeviceCAVLC 1: the CAVLC slice data is written on the
+                                  device (jmh_cavlc_write_slices); the host keeps the slice headers
+                                  and the NAL packaging.  SymbolMode 0, device backend only        */
     int  verbose;
 } jm_input;
 
@@ -164,6 +168,13 @@ void jm_slice_rate_check(const jm_slice_writer *w, long *checked, long *bad);
 /* close the current slice's data in its rbsp and start the next slice (header into rbsp), keeping
    the picture's neighbour buffers (SliceMode 1: one writer per picture, one rbsp per slice) */
 void jm_slice_restart(jm_slice_writer *w, jm_bits *rbsp, const jm_slice *sl);
+/* slice_header (7.3.3) alone: DeviceCAVLC 1 writes the slice data behind it on the device */
+void jm_write_slice_header(jm_bits *rbsp, const jm_seq *s, const jm_slice *sl);
+/* host/cavlc_ref.c: this writer behind the calling convention of jmh_cavlc_write_results, flat
+   arguments (the reference of the device writer's tests): per slice the RBSP bytes after the
+   header's whole bytes.  where[n] is filled whenever the descriptors are valid */
+int  jm_cavlc_ref(int width, int height, int transform_8x8_mode, int constrained_intra, const jmh_mb_result *res, int n,
+                  const jmh_slice_desc *slices, uint8_t *out, size_t cap, jmh_slice_bytes *where);
 
 /* ---- deblocking (H.264 8.7), in place on the reconstructed picture ---------------------- */
 void jm_deblock_picture(jm_pic *p, const jm_seq *s, const jmh_mb_result *const *res, int qp);
@@ -194,6 +205,12 @@ typedef struct jm_backend {
     int (*tq4x4)(void *ctx, int n, const int16_t *resid, const uint8_t *pred, int qp, int intra,
                  int16_t *levels, uint8_t *recon, int32_t *coeff_cost, int32_t *nonzero);
 } jm_backend;
+/* DeviceCAVLC 1: the backend's writer of the CAVLC slice data of the picture last popped / encoded
+   (the product binary registers jmh_cavlc_write_slices; a backend without one, such as the CPU
+   build's, leaves it unset and DeviceCAVLC 1 is rejected).  Kept out of jm_backend so that its
+   positional initialisers stay as they are. */
+typedef int (*jm_cavlc_slices_fn)(void *ctx, int n, const jmh_slice_desc *slices, uint8_t *out, size_t cap, jmh_slice_bytes *where);
+void jm_set_device_cavlc(jm_cavlc_slices_fn fn);
 
 typedef struct jm_stats {
     int frames;

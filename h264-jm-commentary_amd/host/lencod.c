@@ -43,6 +43,9 @@ static int gpu_tq4x4(void *ctx, int n, const int16_t *resid, const uint8_t *pred
                      int32_t *cc, int32_t *nz) {
     return jmh_tq4x4_batch((jmh_ctx *)ctx, n, resid, pred, qp, intra, lev, rec, cc, nz);
 }
+static int gpu_cavlc_slices(void *ctx, int n, const jmh_slice_desc *d, uint8_t *out, size_t cap, jmh_slice_bytes *where) {
+    return jmh_cavlc_write_slices((jmh_ctx *)ctx, n, d, out, cap, where);
+}
 
 int main(int argc, char **argv) {
     jm_input inp;
@@ -60,6 +63,7 @@ int main(int argc, char **argv) {
     jm_backend be = {"mi355x-hip", ctx, gpu_set_ref, gpu_encode, gpu_res, gpu_recon, gpu_destroy,
                      gpu_deblocked, gpu_ref_deblocked, gpu_push, gpu_pop, jmh_pipeline_depth(ctx),
                      gpu_search_pictures, gpu_block_search, gpu_tq4x4};
+    jm_set_device_cavlc(gpu_cavlc_slices);
     if (getenv("JMH_HOST_DEBLOCK")) be.read_deblocked = NULL, be.reference_deblocked = NULL;
     jm_stats st;
     r = jm_encode_sequence(&inp, &be, &st, stdout);

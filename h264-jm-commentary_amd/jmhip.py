@@ -139,8 +139,38 @@ _SIGS = {
 EXPORTED = tuple(_SIGS)
 
 
+# ---- CAVLC slice data on the device (include/jmhip_cavlc.h; additive to ABI 14) ----
+class JmhSliceDesc(ctypes.Structure):
+    _fields_ = [("first_mb", ctypes.c_int32), ("n_mb", ctypes.c_int32), ("slice_type", ctypes.c_int32),
+                ("lead_nbits", ctypes.c_int32), ("lead_bits", ctypes.c_uint32)]
+
+
+class JmhSliceBytes(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("nbytes", ctypes.c_int64), ("nbits", ctypes.c_int64)]
+
+
+JMW_MB_MAX_BITS = 15424          # csrc/jmh_cavlc_write.h: the worst case of one macroblock
+_SIGS_CAVLC = {
+    "jmh_cavlc_write_slices": (_I, [_P, _I, _P, _P, ctypes.c_size_t, _P]),
+    "jmh_cavlc_write_results": (_I, [_P, _P, _I, _P, _P, ctypes.c_size_t, _P]),
+}
+EXPORTED_CAVLC = tuple(_SIGS_CAVLC)
+
+
+def slice_descs(nmb, slice_type, mbs_per_slice=0, lead=()):
+    """Raster runs of mbs_per_slice macroblocks (0: one slice) covering nmb macroblocks, as a
+    JmhSliceDesc array; lead: (lead_nbits, lead_bits) per slice, cycled (default: none)."""
+    step = mbs_per_slice if mbs_per_slice > 0 else nmb
+    firsts = list(range(0, nmb, step))
+    d = (JmhSliceDesc * len(firsts))()
+    for i, f in enumerate(firsts):
+        nb, bits = lead[i % len(lead)] if lead else (0, 0)
+        d[i] = JmhSliceDesc(f, min(step, nmb - f), slice_type, nb, bits & ((1 << nb) - 1))
+    return d
+
+
 class JmhError(RuntimeError):
-    pass
+    status = None                # the JMH_E_* code, where a jmh_* call failed
 
 
 _lib = None
@@ -154,7 +184,7 @@ def load(path=LIB_PATH):
     if not os.path.exists(path):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -167,7 +197,9 @@ def load(path=LIB_PATH):
 
 def _check(st, what):
     if st != JMH_OK:
-        raise JmhError(f"{what}: {STATUS.get(st, st)} ({st})")
+        e = JmhError(f"{what}: {STATUS.get(st, st)} ({st})")
+        e.status = st
+        raise e
 
 
 def _ptr(a):
@@ -354,6 +386,31 @@ class Encoder:
         _check(self.lib.jmh_get_timing(self.ctx, ctypes.byref(t)), "jmh_get_timing")
         return t
 
+    # ---- CAVLC slice data on the device (jmh_cavlc_write_slices / _results) ----
+    def _cavlc(self, call, what, descs, cap, with_where):
+        n = len(descs)
+        if cap is None:          # the documented bound: no picture needs more
+            cap = self.mbw * self.mbh * (JMW_MB_MAX_BITS // 8) + 2 * n
+        out = np.zeros(max(cap, 1), np.uint8)
+        where = (JmhSliceBytes * n)()
+        _check(call(n, ctypes.cast(descs, _P), _ptr(out), cap, ctypes.cast(where, _P)), what)
+        data = [out[w.offset:w.offset + w.nbytes].tobytes() for w in where]
+        return (data, [(w.offset, w.nbytes, w.nbits) for w in where]) if with_where else data
+
+    def cavlc_slices(self, descs, cap=None, with_where=False):
+        """slice_data() + rbsp_trailing_bits of every slice (a JmhSliceDesc array, see slice_descs) of
+        the picture last popped / waited for, written on the device: a list of bytes, one per slice
+        (behind each slice header's whole bytes they are the slice's RBSP)."""
+        return self._cavlc(lambda *a: self.lib.jmh_cavlc_write_slices(self.ctx, *a), "jmh_cavlc_write_slices", descs, cap, with_where)
+
+    def cavlc_results(self, res, descs, cap=None, with_where=False):
+        """The same for caller-supplied results (MB_RESULT_DTYPE[mbw * mbh]); no picture needed."""
+        res = np.ascontiguousarray(res, MB_RESULT_DTYPE)
+        if res.size != self.mbw * self.mbh:
+            raise JmhError(f"cavlc_results: {res.size} results for {self.mbw * self.mbh} macroblocks")
+        return self._cavlc(lambda *a: self.lib.jmh_cavlc_write_results(self.ctx, _ptr(res), *a), "jmh_cavlc_write_results", descs, cap,
+                           with_where)
+
     # ---- unit seams ----
     def sad_table(self, mb_xy, centres):
         mb_xy = np.ascontiguousarray(mb_xy, np.int32)
@@ -454,6 +511,23 @@ def load_host(path=HOST_LIB_PATH):
         _host.jm_synth_frame.restype = None
         _host.jm_synth_frame.argtypes = [_P, _I, _I, ctypes.c_uint64, _I]
     return _host
+
+
+def cavlc_ref(width, height, transform_8x8_mode, constrained_intra, res, descs, with_where=False):
+    """The host writer (host/bitstream.c through host/cavlc_ref.c) behind the arguments of
+    Encoder.cavlc_results: the reference of the device writer.  A list of bytes, one per slice."""
+    host = load_host()
+    host.jm_cavlc_ref.restype = _I
+    host.jm_cavlc_ref.argtypes = [_I, _I, _I, _I, _P, _I, _P, _P, ctypes.c_size_t, _P]
+    res = np.ascontiguousarray(res, MB_RESULT_DTYPE)
+    n = len(descs)
+    cap = res.size * (JMW_MB_MAX_BITS // 8) + 2 * n
+    out = np.zeros(cap, np.uint8)
+    where = (JmhSliceBytes * n)()
+    _check(host.jm_cavlc_ref(width, height, transform_8x8_mode, constrained_intra, _ptr(res), n, ctypes.cast(descs, _P), _ptr(out), cap,
+                             ctypes.cast(where, _P)), "jm_cavlc_ref")
+    data = [out[w.offset:w.offset + w.nbytes].tobytes() for w in where]
+    return (data, [(w.offset, w.nbytes, w.nbits) for w in where]) if with_where else data
 
 
 class _JmPic(ctypes.Structure):

@@ -31,6 +31,10 @@
  * function names above are the JM 8.6 names (tag [J]).  docs/JM_SEMANTICS.md
  * pins every non-normative choice.
  *
+ * CAVLC slice data on the device (the write_one_macroblock loop of slice.c › encode_one_slice with
+ * SymbolMode 0): include/jmhip_cavlc.h, included at the end of this file.  It is additive:
+ * JMH_ABI_VERSION stays 14 and no struct or entry point declared here changes.
+ *
  * Conventions: plain C types only; 0 = OK, negative JMH_E_* on error; nothing throws or aborts
  * across this boundary.  One context = one HIP device + one HIP stream; a context is not
  * thread-safe (JM is single threaded).  Multi-GPU = one process (and one context) per GPU.
@@ -365,4 +369,5 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #ifdef __cplusplus
 }
 #endif
+#include "jmhip_cavlc.h"
 #endif /* JMHIP_H */
