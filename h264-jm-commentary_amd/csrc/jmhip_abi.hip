@@ -968,6 +968,9 @@ static int check_params(const jmh_ctx *c, const jmh_frame_params *fp) {
         fp->lambda_motion > JMH_LAMBDA_MAX) return JMH_E_INVALID_ARG;
     if (fp->deblock && (fp->lf_disable < 0 || fp->lf_disable > 2 || fp->lf_alpha_div2 < -6 || fp->lf_alpha_div2 > 6 ||
                         fp->lf_beta_div2 < -6 || fp->lf_beta_div2 > 6)) return JMH_E_INVALID_ARG;
+    // idc 2 leaves slice edges unfiltered (8.7); deblock_mb filters them, so with more than one
+    // slice per picture it would be idc 0.  One slice per picture: idc 2 == idc 0
+    if (fp->deblock && fp->lf_disable == 2 && c->cfg.slice_mbs > 0 && c->cfg.slice_mbs < c->mbw * c->mbh) return JMH_E_UNSUPPORTED_CFG;
     if (fp->slice_type == JMH_P_SLICE && c->ref_kind == REF_NONE) return JMH_E_STATE;
     // RDOptimization 1: lambda_mode > 0 and its factor (jm_lambda_rdo_on at QP 51 + QpBdOffset 12:
     // lambda = 0.85 * 2^((63 - 12) / 3) = 0.85 * 2^17, factor = 65536 * sqrt(lambda) ~ 2.2e7 < 2^25,

@@ -178,6 +178,11 @@ int  jm_cavlc_ref(int width, int height, int transform_8x8_mode, int constrained
 
 /* ---- deblocking (H.264 8.7), in place on the reconstructed picture ---------------------- */
 void jm_deblock_picture(jm_pic *p, const jm_seq *s, const jmh_mb_result *const *res, int qp);
+/* host/deblock_ref.c: jm_deblock_picture behind flat arguments (the deblocking tests' view of the
+   host filter): contiguous planes of 16 mbw x 16 mbh samples (uint8_t at bit depth 8, uint16_t at
+   9 / 10) filtered in place, res[mbw * mbh] in raster order, disable_deblocking_filter_idc 0 */
+int  jm_deblock_ref(void *y, void *u, void *v, const jmh_mb_result *res, int mbw, int mbh, int qp, int chroma_qp_offset,
+                    int alpha_div2, int beta_div2, int bit_depth);
 
 /* ---- hot-path backend ------------------------------------------------------------------ */
 typedef struct jm_backend {

@@ -530,6 +530,24 @@ def cavlc_ref(width, height, transform_8x8_mode, constrained_intra, res, descs, 
     return (data, [(w.offset, w.nbytes, w.nbits) for w in where]) if with_where else data
 
 
+def deblock_ref(rec_yuv, results, mbw, mbh, qp, chroma_qp_offset=0, alpha_div2=0, beta_div2=0, bit_depth=8):
+    """The host deblocker (host/deblock.c through host/deblock_ref.c) on a reconstructed picture
+    (y, u, v) and its results (MB_RESULT_DTYPE[mbw * mbh]), disable_deblocking_filter_idc 0:
+    the filtered (y, u, v), new arrays."""
+    host = load_host()
+    host.jm_deblock_ref.restype = _I
+    host.jm_deblock_ref.argtypes = [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]
+    res = np.ascontiguousarray(results, MB_RESULT_DTYPE)
+    if res.size != mbw * mbh:
+        raise JmhError(f"deblock_ref: {res.size} results for {mbw * mbh} macroblocks")
+    y, u, v = (np.array(p, np.uint16 if bit_depth > 8 else np.uint8, order="C") for p in rec_yuv)
+    if y.shape != (16 * mbh, 16 * mbw) or u.shape != (8 * mbh, 8 * mbw) or v.shape != u.shape:
+        raise JmhError(f"deblock_ref: planes {y.shape} {u.shape} {v.shape} for {mbw} x {mbh} macroblocks")
+    _check(host.jm_deblock_ref(_ptr(y), _ptr(u), _ptr(v), _ptr(res), mbw, mbh, qp, chroma_qp_offset, alpha_div2, beta_div2, bit_depth),
+           "jm_deblock_ref")
+    return y, u, v
+
+
 class _JmPic(ctypes.Structure):
     _fields_ = [("w", ctypes.c_int), ("h", ctypes.c_int), ("y", _P), ("u", _P), ("v", _P),
                 ("bd", ctypes.c_int), ("Y", _P), ("U", _P), ("V", _P)]

@@ -157,7 +157,10 @@ typedef struct jmh_frame_params {
     int32_t chroma_qp_offset;  /* chroma_qp_index_offset                                         */
     int32_t deblock;           /* 1: also deblock (DeblockFrame, 8.7) on the device into the     */
                                /*    next reference (jmh_read_deblocked, set_reference_slot(-2)) */
-    int32_t lf_disable;        /* disable_deblocking_filter_idc (1: copy, no filtering)          */
+    int32_t lf_disable;        /* disable_deblocking_filter_idc (1: copy, no filtering; 2: accepted
+                                  with one slice per picture, where it equals 0; with several slices
+                                  (jmh_config.slice_mbs below the picture's MBs) the slice edges would
+                                  have to stay unfiltered: JMH_E_UNSUPPORTED_CFG)                    */
     int32_t lf_alpha_div2;     /* slice_alpha_c0_offset_div2                                     */
     int32_t lf_beta_div2;      /* slice_beta_offset_div2                                         */
     int32_t lambda_factor_rd;  /* RDO on: LAMBDA_FACTOR(lambda_motion) = (int)(65536 * sqrt(lambda_rd)
