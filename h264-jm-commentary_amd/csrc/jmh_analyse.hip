@@ -391,12 +391,14 @@ __device__ __forceinline__ void subpel_wave(const DevParams &d, MeS &s, int j, c
 // -> barrier, sub-pel search j on wave j (+ forwarded MVPs), barrier.
 // the wave of a stage's search j: waves 0, 1, 4, 5 (SIMDs 0 and 1) first, so that the Intra4x4
 // waves 6 and 7 (SIMDs 2 and 3) share their SIMDs with no sub-pel wave of the workgroup in stages
-// of up to four searches
+// of up to four searches.  Wave 3 (SIMD 3, wave 7's) has no search in stages of up to five: in
+// k_mb_flow it runs the chroma intra-mode decision in block 0's stage 0 and the Intra16x16 decision
+// in block 3's stage 1 (xdec below: 1 / 0, -1 none), so wave 7 shares its SIMD in those two stages
 __device__ __forceinline__ constexpr int search_wave(int j) { return (0x6325410 >> (4 * j)) & 15; }
 
 template <int NS, bool FWD, class EV, class IDLE>
 __device__ __forceinline__ void me_stage(const DevParams &d, MeS &s, PosState &ps, const SDesc (&sd)[NS], int b8, int best8x8, EV ev,
-                                         int islot, IDLE idle, int wave) {
+                                         int islot, IDLE idle, int wave, int xdec = -1) {
     const int lane = __lane_id();
     fence_state(ps);
     int pmx[NS], pmy[NS];
@@ -434,6 +436,9 @@ __device__ __forceinline__ void me_stage(const DevParams &d, MeS &s, PosState &p
 #pragma unroll
     for (int j = 0; j < NS; j++)
         if (wave == search_wave(j)) subpel_wave(d, s, j, sd[j], pmx[j], pmy[j], ps.scx, ps.scy, b8, best8x8);
+    if constexpr (NS <= 5) {   // wave 3 has no search: intra slot 11, decision xdec
+        if (xdec >= 0 && wave == 3) idle(11, xdec);
+    }
     if constexpr (NS <= 6) {
         if (islot >= 0 && wave >= 6) idle(islot, wave - 6);   // the MB's Intra4x4 on otherwise idle waves
     } else {
@@ -536,8 +541,12 @@ __device__ __forceinline__ void p8x8_block(const DevParams &d, MeS &s, PosState 
     // long enough to hide a step: the multi-search stages 0 and 1 of every block (block 3's stage
     // 0 has one free wave, so its step, 8, is a one-block step), two steps in single-search stages
     constexpr int IS0 = 3 * B8 - (B8 == 3 ? 1 : 0), IS1 = IS0 + 1;
-    // (k_mb_flow: block 2's stage 2, slot 11, the Intra16x16 and chroma intra-mode decisions)
-    constexpr int IS2 = B8 <= 1 ? 3 * B8 + 2 : B8 == 3 ? 10 : 11, IS3 = -1;
+    constexpr int IS2 = B8 <= 1 ? 3 * B8 + 2 : B8 == 3 ? 10 : -1, IS3 = -1;
+    // k_mb_flow: slot 11 on wave 3, the chroma intra-mode decision in block 0's stage 0 and the
+    // Intra16x16 decision in block 3's stage 1 (a 3 us stage) -- they read only the source and the
+    // intra neighbourhood, both loaded before the first stage.  Both decisions in block 0's stage 0,
+    // on waves 2 and 3, stretched that stage by 2 us and measured slower.
+    constexpr int XD0 = B8 == 0 ? 1 : -1;
     const int sr = d.sr;
     fence_state(ps);
     sad_strip<false, 4 * X, 4 * Y, 0, 0>(s, ps);        // the four 4x4 SADs of this 8x8 block
@@ -569,7 +578,7 @@ __device__ __forceinline__ void p8x8_block(const DevParams &d, MeS &s, PosState 
             EV(0, 5, X, Y + 1); EV(1, 6, X + 1, Y); EV(2, 7, X + 1, Y);
             const int rg[2] = {search_range(d, 2), search_range(d, 3)};
             eval_sad8<2, 2, 0, 2, 3, 2, 0>(s, ps, tid, sr, rg, pmx + 3, pmy + 3, bk + 3);
-        }, IS1, idle, wave);
+        }, IS1, idle, wave, 0);
     } else {
         {   // stage 0: 8x8, 8x4 upper, 4x8 left, 4x4 top-left
             const SDesc sd[4] = {{4, X, Y, B8, 0, 0, 0, 0},
@@ -578,7 +587,7 @@ __device__ __forceinline__ void p8x8_block(const DevParams &d, MeS &s, PosState 
                                  {7, X, Y, B8, 7, X + 1, Y, 2}};
             me_stage<4, false>(d, s, ps, sd, B8, best8x8, [&](unsigned (&bk)[4], const int (&pmx)[4], const int (&pmy)[4]) {
                 EV(0, 4, X, Y); EV(1, 5, X, Y); EV(2, 6, X, Y); EV(3, 7, X, Y);
-            }, IS0, idle, wave);
+            }, IS0, idle, wave, XD0);
         }
         {   // stage 1: 8x4 lower, 4x8 right, 4x4 top-right
             const SDesc sd[3] = {{5, X, Y + 1, B8, 0, 0, 0, 0}, {6, X + 1, Y, B8, 0, 0, 0, 0}, {7, X + 1, Y, B8, 7, X, Y + 1, 0}};
@@ -909,12 +918,13 @@ __device__ __forceinline__ void intra_role(const DevParams &d, IntraS<pel> &s, i
 // the Intra4x4 decision inside a motion-search workgroup, on its waves 6 and 7 (w = wave - 6; wave
 // 7 as w = 0 in block 3's first stage) while the sub-pel waves of a stage work; steps are separated
 // by the stage barriers.  Slot
-// k = 0..9: diagonal k of the 4x4 grid; slot 10: the totals and results.
+// k = 0..9: diagonal k of the 4x4 grid; slot 10: the totals and results; slot 11 (k_mb_flow, on
+// wave 3): the Intra16x16 (w = 0) or the chroma intra-mode (w = 1) decision.
 __device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &s, MbScratch *scr, int k, int w, int mbx, int mby) {
     const int lane = threadIdx.x & 63;
     const MbAvail mav = intra_avail(d, mbx, mby);
     const bool avL = mav.L, avT = mav.T, avTL = mav.TL, avTR = mav.TR;
-    if (k == 11) {                                       // k_mb_flow: Intra16x16 (wave 6), chroma (wave 7)
+    if (k == 11) {                                       // k_mb_flow, wave 3: Intra16x16 (w = 0) or chroma (w = 1)
         if (d.i16c) {
             if (w == 0) i16_decision(d, s.org, s.nb, scr, lane, avL, avT, avTL);
             else chroma_decision(d, s.nb, scr, lane, avL, avT, avTL);
@@ -1105,8 +1115,9 @@ __device__ __forceinline__ bool flow_done(const FlowArgs &f, int e, int mb, uint
 // right edge) neighbours and the reference picture's MB (x+5, y+5) (PIPE_LAG's reach, clamped) must
 // be done -- the rest of the wavefront's dependencies follow from theirs; a claimed ticket belongs
 // to a running workgroup and waits only on smaller tickets, so every wait ends.  Then the P
-// macroblock's me_mb (41 searches + Intra4x4), its Intra16x16 / chroma decisions on waves 0 / 1 (an
-// I macroblock: intra_role), and final_core on all 512 threads.  Publication: every wave's stores
+// macroblock's me_mb (41 searches + Intra4x4, and its Intra16x16 / chroma decisions on wave 3
+// beside two search stages; an I macroblock: intra_role), and final_core on all 512 threads.
+// Publication: every wave's stores
 // drained, the workgroup barrier, one agent-scope release, the flag; a waiter polls relaxed, then
 // one agent-scope acquire before the workgroup reads (MI355X_MICROARCH.md, inter-workgroup
 // visibility).

@@ -12,7 +12,9 @@ Model (calibrated on the measured steady-state tick, DESIGN.md §5.1, JMH_BLOCK_
 - dataflow: a free slot claims the next MB in tick order (the order the host issues ticks, lag
   PIPE_LAG = 16), waits (holding its slot) until its left and top-right neighbours (top at the
   right edge) and the reference picture's MB (x+5, y+5) (clamped) are done, then runs search +
-  rest on that slot; SYNC us of flag hand-off per MB;
+  rest on that slot; SYNC us of flag hand-off per MB; --fixed --slots N asks what N slots per CU
+  could give if a workgroup's measured times did not grow with its neighbours (the dependency
+  bound alone);
 - tick model (for calibration): every tick runs its MBs two per CU, the tick ends with the
   slowest, then a final launch (FIN us) and the launch gaps (GAP us).
 
@@ -92,6 +94,8 @@ def sim_dataflow(a, ticks, npics):
 
     def rates(c):
         run = [w for w in cus[c] if w[3]]
+        if a.fixed:
+            return {id(w): 1.0 for w in run}
         if len(run) == 1:
             return {id(run[0]): 1.0}
         if len(run) == 2:
@@ -145,8 +149,8 @@ def sim_dataflow(a, ticks, npics):
         try_start(c, w)
 
     for c in range(ncu):
-        claim(c)
-        claim(c)
+        for _ in range(a.slots):
+            claim(c)
         schedule(c)
     pic_done = {}
     cnt = {}
@@ -214,7 +218,13 @@ def main():
     ap.add_argument("--fin", type=float, default=17.0)
     ap.add_argument("--gap", type=float, default=5.0)
     ap.add_argument("--pics", type=int, default=24)
+    ap.add_argument("--slots", type=int, default=2, help="workgroups per CU (more than 2 needs --fixed)")
+    ap.add_argument("--fixed", action="store_true",
+                    help="every running workgroup at rate 1: --ws / --wf are times measured under load (JMH_FLOW_PROF), "
+                         "so more slots per CU cost nothing -- an upper bound for them")
     a = ap.parse_args()
+    if a.slots > 2 and not a.fixed:
+        ap.error("--slots > 2 has no sharing model: use --fixed")
     ticks = tick_order(a.pics)
     pt, nt = sim_ticks(a, ticks, a.pics)
     mp = 1920 * 1080 / 1e6
