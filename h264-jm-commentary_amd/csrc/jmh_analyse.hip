@@ -658,14 +658,13 @@ __device__ __forceinline__ void chroma_decision(const DevParams &d, const IntraN
             }
         sat = satd4x4(df, d.use_hadamard);
     }
-    const bool cav[4] = {true, avL, avT, avT && avL && avTL};
     int minc = BIGCOST, c_mode = 0;
 #pragma unroll
     for (int m = 0; m < 4; m++) {
         int c = 0;
 #pragma unroll
         for (int q = 0; q < 8; q++) c += __builtin_amdgcn_readlane(sat, 8 * m + q);
-        if (cav[m] && c < minc) { minc = c; c_mode = m; }
+        if (chroma_mode_ok(m, avL, avT, avTL) && c < minc) { minc = c; c_mode = m; }
     }
     if (lane == 0) scr->c_mode = c_mode;
 }

@@ -18,13 +18,6 @@ struct IntraS {
 // ======================================================================================
 //  role 0: Intra4x4 (Mode_Decision_for_Intra4x4Macroblock) in 10 diagonal steps
 // ======================================================================================
-template <class pel>
-__device__ __forceinline__ int lpix(const IntraS<pel> &s, int x, int y) {
-    if (y < 0) return s.nb.rtop[x + 1];
-    if (x < 0) return s.nb.rleft[y];
-    return s.rec[16 * y + x];
-}
-
 // lane_fwd4x4 / lane_inv4x4 with the row gathers as quad DPP broadcasts (the four samples of
 // row y of a 16-lane group are one quad); the column gathers stay ds_bpermute (whole quads active);
 // the outputs of each butterfly stage by fwd_tap / inv_tap (jmh_common.h)
@@ -66,6 +59,7 @@ __device__ __forceinline__ void i4_block(const DevParams &d, IntraS<pel> &s, MbS
     const int lane = threadIdx.x & 63, l = lane & 15;
     const int bx = 4 * bx4, by = 4 * by4, blk = 4 * by4 + bx4;
     const int lambda = d.lambda_mode, qp = d.qp + d.qpbd, had = d.use_hadamard;
+    // i4_avail (jmh_intra.h), spelled out: through the call k_mb_intra takes 4 B more scratch
     const bool up = by > 0 || avT, left = bx > 0 || avL;
     const bool ul = (bx > 0 && by > 0) || (bx == 0 && by > 0 && avL) || (bx > 0 && by == 0 && avT) || (bx == 0 && by == 0 && avTL);
     bool ur = by == 0 ? (bx + 4 <= 15 ? avT : avTR) : (bx + 4 <= 15);
@@ -87,7 +81,7 @@ __device__ __forceinline__ void i4_block(const DevParams &d, IntraS<pel> &s, MbS
     const int v = pav ? raw : 0;
     const int upM = by > 0 ? s.ipred_cur[blk - 4] : s.bd.ipm[1 + bx4];
     const int leftM = bx > 0 ? s.ipred_cur[blk - 1] : s.bd.ipm[6 + by4];
-    const int mpm = (upM < 0 || leftM < 0) ? 2 : min(upM, leftM);
+    const int mpm = intra_mpm(upM, leftM);
     const int m = lane >> 2, y = lane & 3;
     int o[4];
     if constexpr (sizeof(pel) == 1) {         // the row's four samples in one dword
@@ -131,8 +125,7 @@ __device__ __forceinline__ void i4_block(const DevParams &d, IntraS<pel> &s, MbS
     t += dpp<0xB1>(t);                        // the quad's rows
     t += dpp<0x4E>(t);
     const int sat = had ? t >> 1 : t;
-    const bool avm = m == 2 || ((m == 0 || m == 3 || m == 7) && up) || ((m == 1 || m == 8) && left) || (up && left && ul);
-    const int cst = (m < 9 && avm) ? (m == mpm ? 0 : 4 * lambda) + sat : BIGCOST;
+    const int cst = (m < 9 && intra_mode_ok(m, up, left, ul)) ? (m == mpm ? 0 : 4 * lambda) + sat : BIGCOST;
     const unsigned key = wave_min_u32((y == 0 && cst < BIGCOST) ? ((unsigned)cst << 4) | (unsigned)m : 0xFFFFFFFFu);
     I4ST(54, key);
     const int best = key == 0xFFFFFFFFu ? 0 : (int)(key & 15u), bc = key == 0xFFFFFFFFu ? BIGCOST : (int)(key >> 4);
@@ -160,4 +153,3 @@ __device__ __forceinline__ void i4_block(const DevParams &d, IntraS<pel> &s, MbS
     acc[0] += bc;
     if (nz) { acc[1] |= 1 << ((by4 >> 1) * 2 + (bx4 >> 1)); acc[2] |= 1 << blk; }
 }
-

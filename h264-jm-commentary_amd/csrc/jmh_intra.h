@@ -56,6 +56,103 @@ __device__ __forceinline__ void load_orgc(const DevParams &d, IntraNb<pel> &nb, 
     nb.orgc[uv][k] = spl<pel>(uv ? d.orgV : d.orgU)[((8 * mby) + (k >> 3)) * d.Wc + 8 * mbx + (k & 7)];
 }
 
+// ---- the intra neighbour rules, stated once for every kernel that decides an intra mode
+// Mode m in [0, 9) of an Intra4x4 / Intra8x8 block (8.3.1.2 / 8.3.2.2: 2 DC; 0, 3, 7 need the row above,
+// 1, 8 the left column, 4..6 both and the corner).  A caller whose m is a lane index guards m < 9 itself.
+__host__ __device__ constexpr bool intra_mode_ok(int m, bool up, bool left, bool ul) {
+    return m == 2 || ((m == 0 || m == 3 || m == 7) && up) || ((m == 1 || m == 8) && left) || (up && left && ul);
+}
+// intra_chroma_pred_mode m (8.3.4: 0 DC, 1 horizontal, 2 vertical, 3 plane) and Intra16x16PredMode m
+// (8.3.3: 0 vertical, 1 horizontal, 2 DC, 3 plane) from the macroblock's neighbours
+__host__ __device__ constexpr bool chroma_mode_ok(int m, bool avL, bool avT, bool avTL) { return m == 0 || (m == 1 ? avL : m == 2 ? avT : avT && avL && avTL); }
+__host__ __device__ constexpr bool i16_mode_ok(int m, bool avL, bool avT, bool avTL) { return m == 2 || (m == 0 ? avT : m == 1 ? avL : avT && avL && avTL); }
+// predIntra4x4PredMode / predIntra8x8PredMode (8.3.1.1 / 8.3.2.1) from the left and upper blocks' modes (-1: none,
+// so DC), and rem_intra_pred_mode of mode m against it (-1: prev_intra_pred_mode_flag, the predicted mode itself)
+__host__ __device__ constexpr int intra_mpm(int a, int b) { return (a < 0 || b < 0) ? 2 : a < b ? a : b; }
+__host__ __device__ constexpr int intra_rem(int m, int mpm) { return m == mpm ? -1 : m < mpm ? m : m - 1; }
+
+// which neighbours of a block inside the macroblock are available (6.4.11.4 / 6.4.11.2): the
+// macroblock's own earlier blocks, else the neighbouring macroblock's MbAvail flag
+struct BlkAvail { bool up, left, ul, ur; };
+// the 4x4 block at sample (bx, by) in {0, 4, 8, 12}^2: below the first row an odd block's upper right comes later
+__host__ __device__ constexpr BlkAvail i4_avail(int bx, int by, const MbAvail &mav) {
+    return {by > 0 || mav.T, bx > 0 || mav.L,
+            (bx > 0 && by > 0) || (bx == 0 && by > 0 && mav.L) || (bx > 0 && by == 0 && mav.T) || (bx == 0 && by == 0 && mav.TL),
+            (by == 0 ? (bx + 4 <= 15 ? mav.T : mav.TR) : (bx + 4 <= 15)) && !((bx == 4 || bx == 12) && (by == 4 || by == 12))};
+}
+// the 8x8 block b8 (raster)
+__host__ __device__ constexpr BlkAvail i8_avail(int b8, const MbAvail &mav) {
+    return {(b8 & 2) ? true : mav.T, (b8 & 1) ? true : mav.L, b8 == 3 ? true : b8 == 1 ? mav.T : b8 == 2 ? mav.L : mav.TL,
+            b8 == 0 ? mav.T : b8 == 1 ? mav.TR : b8 == 2};
+}
+
+namespace intra_rules_check {   // the small domains, enumerated on every compile
+constexpr bool mode_ok_all() {   // m in [0, 9) x the 8 flag sets, against the spellings the 4x4 and the 8x8 sites had
+    for (int m = 0; m < 9; m++)
+        for (int f = 0; f < 8; f++) {
+            const bool up = f & 1, left = f & 2, ul = f & 4, dir = ((m == 0 || m == 3 || m == 7) && up) || ((m == 1 || m == 8) && left);
+            if (intra_mode_ok(m, up, left, ul) != (m == 2 || dir || (up && left && ul)) ||
+                intra_mode_ok(m, up, left, ul) != (m == 2 || dir || ((m == 4 || m == 5 || m == 6) && up && left && ul)))
+                return false;
+        }
+    return true;
+}
+constexpr bool mpm_rem_all() {   // modes -1..8: rem skips the predicted mode, so it fits 3 bits and decodes back (7.4.5.1)
+    for (int a = -1; a < 9; a++)
+        for (int b = -1; b < 9; b++) {
+            const int p = intra_mpm(a, b), r = intra_rem(b, a);
+            if (p != ((a < 0 || b < 0) ? 2 : (a < b ? a : b))) return false;
+            if (a >= 0 && b >= 0 && (a == b ? r != -1 : (r < 0 || r > 7 || (r < a ? r : r + 1) != b))) return false;
+        }
+    return true;
+}
+constexpr bool i4_ur_all() {   // 8.3.1.2 with avT = avTR = true: blkIdx 3, 7, 11, 13, 15 have no upper-right block
+    for (int k = 0; k < 16; k++)   // bit 4 by4 + bx4
+        if (i4_avail(4 * (k & 3), 4 * (k >> 2), MbAvail{false, true, false, true}).ur != (((0x575F >> k) & 1) != 0)) return false;
+    return true;
+}
+static_assert(mode_ok_all(), "intra_mode_ok differs from the Intra4x4 / Intra8x8 spellings on m in [0, 9)");
+static_assert(mpm_rem_all(), "intra_mpm / intra_rem over modes -1..8");
+static_assert(i4_ur_all(), "i4_avail: the upper-right flags");
+}   // namespace intra_rules_check
+
+// a luma sample of the macroblock being decided (s.rec: 16 x 16, stride 16) or of its top / left neighbours (s.nb)
+template <class S>
+__device__ __forceinline__ int lpix(const S &s, int x, int y) {
+    if (y < 0) return s.nb.rtop[x + 1];
+    if (x < 0) return s.nb.rleft[y];
+    return s.rec[16 * y + x];
+}
+
+// The Intra8x8 reference edge of one 8x8 block (8.3.2.2.1): [7 - y] the left column, [8] the corner,
+// [9 + x] the row above and above-right.  By threads t (those >= 25 idle), the caller's barrier between the steps:
+// i8_edge_load (rec: the macroblock's Intra8x8 reconstruction so far, recY: the picture's), i8_edge_filter, i8_edge_dc.
+struct I8Edge { int raw[25], av[25], f[25]; };
+template <class pel>
+__device__ __forceinline__ void i8_edge_load(I8Edge &e, int t, int b8, const BlkAvail &v, const pel *rec, const pel *recY, int pix_x, int pix_y, int W) {
+    if (t >= 25) return;
+    const int bx = 8 * (b8 & 1), by = 8 * (b8 >> 1);
+    int xm, ym;
+    bool a;
+    if (t < 8) { xm = bx - 1; ym = by + 7 - t; a = v.left; }
+    else if (t == 8) { xm = bx - 1; ym = by - 1; a = v.ul; }
+    else { const int xx = t - 9; xm = bx + (xx < 8 || v.ur ? xx : 7); ym = by - 1; a = v.up; }
+    int s = 0;
+    if (a) s = (xm >= 0 && xm < 16 && ym >= 0) ? rec[ym * 16 + xm] : recY[(pix_y + ym) * W + pix_x + xm];
+    e.raw[t] = s; e.av[t] = a;
+}
+__device__ __forceinline__ void i8_edge_filter(I8Edge &e, int t) {   // [1 2 1] along the edge, the ends repeated
+    if (t >= 25 || !e.av[t]) return;
+    const int c = e.raw[t];
+    const int lo = t > 0 && e.av[t - 1] ? e.raw[t - 1] : c, hi = t < 24 && e.av[t + 1] ? e.raw[t + 1] : c;
+    e.f[t] = (lo + 2 * c + hi + 2) >> 2;
+}
+__device__ __forceinline__ int i8_edge_dc(const I8Edge &e, bool up, bool left, int maxv) {
+    int st = 0, sl = 0;
+    for (int i = 0; i < 8; i++) { st += up ? e.f[9 + i] : 0; sl += left ? e.f[i] : 0; }
+    return up && left ? (st + sl + 8) >> 4 : up ? (st + 4) >> 3 : left ? (sl + 4) >> 3 : (maxv + 1) >> 1;
+}
+
 // intrapred_luma_16x16 + find_sad_16x16 on one wave (4 modes x 16 blocks = 64 lanes): the
 // find_sad_16x16 cost and mode, wave-uniform.  The prediction's parameters (8.3.3: the DC sums and
 // the plane's H / V) come from lane reductions -- lanes 0..15 hold p[k, -1], 16..31 p[-1, k]:
@@ -109,17 +206,15 @@ __device__ __forceinline__ void i16_pick(const DevParams &d, const pel *org, con
         acs += abs(o1) + abs(o2) + abs(o3);
     }
     const int cost = row16_sum(acs) + lane_had_abs(dcc / 4, b);
-    const bool av16[4] = {avT, avL, true, avT && avL && avTL};
     int best = MAX_VALUE, i16mode = 2;
 #pragma unroll
     for (int k2 = 0; k2 < 4; k2++) {
         const int c = __builtin_amdgcn_readlane(cost, 16 * k2);
-        if (av16[k2] && c < best) { best = c; i16mode = k2; }
+        if (i16_mode_ok(k2, avL, avT, avTL) && c < best) { best = c; i16mode = k2; }
     }
     cost16 = best / 2;
     mode16 = i16mode;
 }
-
 
 // the Intra16x16 DC path of dct_luma_16x16 [J] on one lane: dc[16] (the blocks' DC coefficients,
 // raster) -> the 4x4 Hadamard, the DC levels (scan order) in dclev and the dequantised DCs in dcdq

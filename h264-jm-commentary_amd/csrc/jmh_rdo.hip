@@ -42,12 +42,24 @@ __device__ __forceinline__ void jmr_lds_tables_load(int t, int n) {
     }
 }
 
-// luma candidates: 0 P_Skip, 1 16x16, 2 16x8, 3 8x16, 4 P8x8, 5 I16MB, 6 I4MB, 7 I8MB; Transform8x8Mode:
-// 8..10 the 16x16 / 16x8 / 8x16 and 11 the (all sub-modes 8x8) P8x8 with the 8x8 transform
-#define RD_NL 12
+// luma candidates (RdoScr.L): the inter ones 1..4 are numbered as their mb_type / the searches' block type;
+// Transform8x8Mode adds I8MB and the inter ones again with the 8x8 transform (P8x8: all sub-modes 8x8)
+enum { RD_SKIP, RD_16x16, RD_16x8, RD_8x16, RD_P8x8, RD_I16, RD_I4, RD_I8, RD_16x16_T8, RD_16x8_T8, RD_8x16_T8, RD_P8x8_T8, RD_NL };
+enum { RD_NBASE = RD_P8x8 + 1, RD_NINTRA = RD_I8 - RD_I16 + 1 };   // inter bases (their chroma), intra luma candidates
 #define RD_NCAND 21   // macroblock-loop candidates: 9 inter + (I16, I4, I8) x 4 chroma modes
-__device__ __forceinline__ int rd_cbase(int i) { return i >= 8 ? i - 7 : i; }   // an inter candidate's base / chroma
-__device__ __forceinline__ bool rd_t8(int i) { return i >= 7; }                 // luma with the 8x8 transform
+__device__ __forceinline__ bool rd_is_intra(int i) { return i >= RD_I16 && i <= RD_I8; }
+__device__ __forceinline__ int rd_with_t8(int c) { return c + (RD_16x16_T8 - RD_16x16); }   // inter candidate c's 8x8-transform twin
+__device__ __forceinline__ int rd_cbase(int i) { return i >= RD_16x16_T8 ? i - (RD_16x16_T8 - RD_16x16) : i; }   // an inter candidate's base / chroma slot
+__device__ __forceinline__ bool rd_t8(int i) { return i >= RD_I8; }                    // luma with the 8x8 transform
+__device__ __forceinline__ int rd_mb_type(int i) {
+    const int b = rd_cbase(i);
+    return i == RD_SKIP ? JMH_PSKIP : b == RD_P8x8 ? JMH_P8x8 : i == RD_I16 ? JMH_I16MB : i == RD_I4 ? JMH_I4MB : i == RD_I8 ? JMH_I8MB : b;
+}
+__device__ __forceinline__ int rd_cintra(int cm) { return RD_NBASE + cm; }                    // RdoScr.C of intra chroma mode cm
+__device__ __forceinline__ int rd_rslot(int i, int cm) { return 4 * (i - RD_I16) + cm; }   // RdoScr.R of intra candidate i with it
+// LumaResidualCoding [J]: an inter 8x8 block / macroblock whose coefficient cost is not above these is zeroed
+#define LUMA_COEFF_COST 4      // _LUMA_COEFF_COST_
+#define LUMA_MB_COEFF_COST 5   // _LUMA_MB_COEFF_COST_
 
 // J = D + lambda * R in double, no contraction (the oracle's gcc x86-64 build has none either)
 __device__ __forceinline__ double rd_cost(int dist, int bits, double lambda) {
@@ -99,8 +111,8 @@ struct RdoRate {
 template <class pel>
 struct RdoScr {
     RdoLuma<pel> L[RD_NL];
-    RdoChroma<pel> C[9];          // [0..4]: chroma of L[0..4] (and of L[8..11]); [5 + m]: intra chroma mode m
-    RdoRate R[12];                // [m]: I16MB with chroma mode m, [4 + m]: I4MB, [8 + m]: I8MB (available modes only)
+    RdoChroma<pel> C[RD_NBASE + 4];   // [rd_cbase(i)]: chroma of inter candidate i; [rd_cintra(m)]: intra chroma mode m
+    RdoRate R[4 * RD_NINTRA];     // [rd_rslot(i, m)]: intra candidate i with chroma mode m (available modes only)
 };
 size_t jmh_rdo_scratch_bytes() { return sizeof(RdoScr<uint16_t>); }
 
@@ -118,15 +130,64 @@ __device__ __forceinline__ uint32_t rdo_state_load(const DevParams &d, int a, ui
     for (int i = t; i < JMR_NCTX / 4; i += n) reinterpret_cast<uint32_t *>(st)[i] = src[i];
     return d.rp->range[slice];
 }
-// the neighbours' context-selection records (A left, B above; flags 0 when not available)
-__device__ __forceinline__ void rdo_nb_load(const DevParams &d, int mbx, int mby, jmr_mbinfo &A, jmr_mbinfo &B, int &hasA, int &hasB, int t) {
-    const MbAvail mav = mb_avail(d, mbx, mby);
-    const int a = mby * d.mbw + mbx, nw = (int)sizeof(jmr_mbinfo) / 4;
+// the neighbours' context-selection records (A left, B above, where mav = mb_avail has them) of macroblock a, by threads t >= 0
+__device__ __forceinline__ void rdo_nb_load(const DevParams &d, int a, const MbAvail &mav, jmr_mbinfo &A, jmr_mbinfo &B, int t) {
+    const int nw = (int)sizeof(jmr_mbinfo) / 4;
     if (t < nw) {
         if (mav.L) reinterpret_cast<uint32_t *>(&A)[t] = reinterpret_cast<const uint32_t *>(d.rp->mbi + a - 1)[t];
         if (mav.T) reinterpret_cast<uint32_t *>(&B)[t] = reinterpret_cast<const uint32_t *>(d.rp->mbi + a - d.mbw)[t];
     }
-    if (t == 0) { hasA = mav.L; hasB = mav.T; }
+}
+// each of n rate lanes its own copy stc[k] of the coding state st0, by threads t of nt
+__device__ __forceinline__ void rdo_state_fan(uint8_t (*stc)[JMR_NCTX], const uint8_t *st0, int n, int t, int nt) {
+    for (int k = t; k < n * (JMR_NCTX / 4); k += nt) {
+        const int m = k / (JMR_NCTX / 4), j = k - m * (JMR_NCTX / 4);
+        reinterpret_cast<uint32_t *>(stc[m])[j] = reinterpret_cast<const uint32_t *>(st0)[j];
+    }
+}
+// JM's scan of J = dist + lambda * bits over the entries i < n that ok(i) admits: strict '<' in index order (none
+// admitted: none).  k_rdo_intra's ok captures by value (by reference its T8 CAVLC instantiations take 2 more VGPRs)
+template <class Ok>
+__device__ __forceinline__ int rd_argmin(const int *dist, const int *bits, int n, double lambda, int none, Ok ok) {
+    double best = 1e30;
+    int bi = none;
+    for (int i = 0; i < n; i++) {
+        if (!ok(i)) continue;
+        const double rd = rd_cost(dist[i], bits[i], lambda);
+        if (rd < best) { best = rd; bi = i; }
+    }
+    return bi;
+}
+// a candidate's syntax for jmr_mb / jmv_mb: the header from its luma and chroma records (cm: the intra
+// chroma mode; b8mode null: none), the levels from sl / sc (the same records, or k_rdo_final's LDS copies)
+template <class pel, class SL, class SC>
+__device__ __forceinline__ void rdo_cand_fill(jmr_cand &r, int mb_type, const RdoLuma<pel> &L, const RdoChroma<pel> &C, int cm, bool t8, const int8_t *b8mode,
+                                              const SL &sl, const SC &sc, int16_t (*mvw)[2]) {
+    r.mb_type = mb_type;
+    r.cbp = L.cbp | C.cbpc << 4;
+    r.i16mode = L.i16mode;
+    r.cmode = cm;
+    r.t8 = t8;
+    for (int q = 0; q < 4; q++) r.b8mode[q] = b8mode ? b8mode[q] : 0;
+    r.ipm = sl.ipm;
+    r.mvd = sl.mvd;
+    r.luma = sl.luma;
+    r.luma_dc = sl.luma_dc;
+    r.cdc = sc.dc;
+    r.cac = sc.ac;
+    r.mvw = mvw;
+}
+// closes luma candidate L on one wave: its reconstruction from rec, the SSD against org, the header
+template <class pel>
+__device__ __forceinline__ void rdo_luma_close(RdoLuma<pel> &L, const pel *rec, const pel *org, int cbp, int cbp_blk, int lane) {
+    int e2 = 0;
+    for (int i = lane; i < 256; i += 64) {
+        L.rec[i] = rec[i];
+        const int e = (int)org[i] - (int)rec[i];
+        e2 += e * e;
+    }
+    const int dist = wave_sum(e2);
+    if (lane == 0) { L.cbp = cbp; L.cbp_blk = cbp_blk; L.dist = dist; L.i16mode = 0; }
 }
 // ChromaResidualCoding [J] of one candidate on ONE wave, a component per pass (lane = 4x4 block
 // cb4 x 16 + l): prediction = intra mode cm (nb) or the MC of fmv; skipped (P_Skip): no residual.
@@ -254,7 +315,7 @@ __device__ __forceinline__ void luma_inter(const DevParams &d, RdoInterS<pel> &s
             int dq, cc;
             const unsigned nz = lane_quant(c, l, qp, rnd, false, lev[i], dq, cc);
             rv[i] = lane_inv4x4(dq, l, pr[i], maxv);
-            if (l == 0) { s.bcost[blk] = (int16_t)min(cc, 32767); s.bnz[blk] = nz != 0; }   // saturated: only its sums are compared (with 4 and 5)
+            if (l == 0) { s.bcost[blk] = (int16_t)min(cc, 32767); s.bnz[blk] = nz != 0; }   // saturated: only its sums are compared (with the two thresholds)
         }
     }
     int cbp = 0, cbp_blk = 0;
@@ -265,7 +326,7 @@ __device__ __forceinline__ void luma_inter(const DevParams &d, RdoInterS<pel> &s
             const int base = (b8 >> 1) * 8 + (b8 & 1) * 2;
             int c8 = s.bcost[base] + s.bcost[base + 1] + s.bcost[base + 4] + s.bcost[base + 5];
             const int nz8 = s.bnz[base] | s.bnz[base + 1] | s.bnz[base + 4] | s.bnz[base + 5];
-            if (c8 <= 4) c8 = 0;                         // _LUMA_COEFF_COST_
+            if (c8 <= LUMA_COEFF_COST) c8 = 0;
             else {
                 keep8 |= 1 << b8;
                 if (nz8) cbp |= 1 << b8;
@@ -276,7 +337,7 @@ __device__ __forceinline__ void luma_inter(const DevParams &d, RdoInterS<pel> &s
             }
             sum_cnt += c8;
         }
-        if (sum_cnt <= 5) { keep8 = 0; cbp = 0; cbp_blk = 0; }   // _LUMA_MB_COEFF_COST_
+        if (sum_cnt <= LUMA_MB_COEFF_COST) { keep8 = 0; cbp = 0; cbp_blk = 0; }
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int blk = 4 * i + (lane >> 4);
@@ -318,14 +379,14 @@ __device__ __forceinline__ void luma_inter8(const DevParams &d, RdoInterS<pel> &
     wave_lds_sync();
     int sum = 0, keep = 0, cbp = 0, cbp_blk = 0;        // wave-uniform
     for (int b8 = 0; b8 < 4; b8++) {
-        const int c8 = s.cost8[b8] <= 4 ? 0 : s.cost8[b8];   // _LUMA_COEFF_COST_
+        const int c8 = s.cost8[b8] <= LUMA_COEFF_COST ? 0 : s.cost8[b8];
         if (c8) {
             keep |= 1 << b8;
             if (s.blk8[b8]) { cbp |= 1 << b8; cbp_blk |= 0x33 << ((b8 >> 1) * 8 + (b8 & 1) * 2); }
         }
         sum += c8;
     }
-    if (sum <= 5) keep = cbp = cbp_blk = 0;             // _LUMA_MB_COEFF_COST_
+    if (sum <= LUMA_MB_COEFF_COST) keep = cbp = cbp_blk = 0;
     int e2 = 0;
     for (int i = lane; i < 256; i += 64) {
         const int b8 = ((i >> 7) << 1) + ((i & 15) >> 3), kb = (keep >> b8) & 1;
@@ -345,7 +406,6 @@ template <class pel, bool T8, bool FFS>
 __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> &s, RdoScr<pel> *scr, uint8_t *ftab_, int mbx, int mby, int lane) {
     uint8_t *const ftab = FFS ? ftab_ : nullptr;
     const int a = mby * d.mbw + mbx, pix_x = 16 * mbx, pix_y = 16 * mby, qp = d.qp + d.qpbd, maxv = d.maxv;
-    const MbAvail mav = mb_avail(d, mbx, mby);
     const bool prof = d.prof && lane == 0 && d.prof_mb == a;   // debug (JMH_PHASE_PROF): stamps 40..52
     PSTAMP(40);
     RdoP8Tmp *tp;
@@ -361,19 +421,12 @@ __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> 
     // ---- inputs: the searches' window, chroma, the coding state, the neighbours' records
     const EWin<pel> wn = epzs_load_mb(d, s.e, mbx, mby, lane);
     jmr_lds_tables_load(lane, 64);
-    int hasA = 0, hasB = 0;
     const uint32_t rg0 = rdo_state_load(d, a, s.st0, lane, 64);
-    {
-        const int nw = (int)sizeof(jmr_mbinfo) / 4;
-        hasA = mav.L; hasB = mav.T;
-        if (lane < nw) {
-            if (hasA) reinterpret_cast<uint32_t *>(&s.nbA)[lane] = reinterpret_cast<const uint32_t *>(d.rp->mbi + a - 1)[lane];
-            if (hasB) reinterpret_cast<uint32_t *>(&s.nbB)[lane] = reinterpret_cast<const uint32_t *>(d.rp->mbi + a - d.mbw)[lane];
-        }
-    }
+    const MbAvail mav = mb_avail(d, mbx, mby);
+    rdo_nb_load(d, a, mav, s.nbA, s.nbB, lane);
     wave_lds_sync();
     PSTAMP(41);
-    const jmr_mbinfo *A = hasA ? &s.nbA : nullptr, *B = hasB ? &s.nbB : nullptr;
+    const jmr_mbinfo *A = mav.L ? &s.nbA : nullptr, *B = mav.T ? &s.nbB : nullptr;
     // SearchMode 0: the SAD tables of the 41 searches (SetupFastFullPelSearch [J]) around the FFS
     // centre, before the first
     int fcx = 0, fcy = 0;
@@ -496,7 +549,7 @@ __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> 
                 const int kq = (Y + (q >> 1)) * 4 + X + (q & 1);
                 if (__builtin_amdgcn_readlane((int)nz, 16 * q)) blk |= 1 << kq;
             }
-            if (cost <= 4) { cost = 0; blk = 0; lev = 0; rv = p; }   // _LUMA_COEFF_COST_
+            if (cost <= LUMA_COEFF_COST) { cost = 0; blk = 0; lev = 0; rv = p; }
             tp->lev8[w][b4][l] = (int16_t)lev;
             px8->pred8[w][q8] = (pel)p;
             px8->rec8[w][q8] = (pel)rv;
@@ -508,11 +561,7 @@ __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> 
                 tp->mvd8[w][lane][1] = (int16_t)(s.e.all_mv[sm][kk][1] - s.pmv[sm][kk][1]);
             }
         }
-        if (!d.cavlc)
-            for (int i = lane; i < JMR_NCTX; i += 64) {   // each rate lane's copy of the running state
-                const int w = i / (JMR_NCTX / 4), j = i % (JMR_NCTX / 4);
-                reinterpret_cast<uint32_t *>(tp->stc[w])[j] = reinterpret_cast<const uint32_t *>(s.strun)[j];
-            }
+        if (!d.cavlc) rdo_state_fan(tp->stc, s.strun, 4, lane, 64);   // the running state
         wave_lds_sync();
         if (l == 0 && inter_on(d.isr, 4 + b4)) {        // RDCost_for_8x8blocks' rate, sub-mode 4 + b4
             const int w = b4;
@@ -528,13 +577,7 @@ __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> 
             }
         }
         wave_lds_sync();
-        double best = 1e30;                             // wave-uniform decision
-        int bm = 0;
-        for (int w = 0; w < 4; w++)
-            if (inter_on(d.isr, 4 + w)) {
-                const double rd = rd_cost(s.dist8[w], s.bits8[w], d.lambda_rd);
-                if (rd < best) { best = rd; bm = w; }
-            }
+        const int bm = rd_argmin(s.dist8, s.bits8, 4, d.lambda_rd, 0, [&](int w) { return inter_on(d.isr, 4 + w); });   // wave-uniform
         best8x8 |= (4 + bm) << (4 * b8);
         if (!d.cavlc) rgrun = s.rgc[bm];
         if (s.cost8[bm]) { p8cbp |= 1 << b8; p8blk |= s.blk8[bm]; p8cnt += s.cost8[bm]; }
@@ -552,23 +595,16 @@ __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> 
     }
     RdoLuma<pel> *L = scr->L;
     if (p8) {                                           // SetCoeffAndReconstruction8x8
-        const bool zero = p8cnt <= 5;                   // _LUMA_MB_COEFF_COST_
-        int e2 = 0;
-        for (int i = lane; i < 256; i += 64) {
-            const pel rv = zero ? s.p8pred[i] : s.p8rec[i];
-            L[4].rec[i] = rv;
-            L[4].luma[i >> 4][i & 15] = zero ? 0 : s.p8lev[i >> 4][i & 15];
-            const int e = (int)s.e.org[i] - (int)rv;
-            e2 += e * e;
-        }
+        RdoLuma<pel> &P = L[RD_P8x8];
+        const bool zero = p8cnt <= LUMA_MB_COEFF_COST;
+        for (int i = lane; i < 256; i += 64) P.luma[i >> 4][i & 15] = zero ? 0 : s.p8lev[i >> 4][i & 15];
         if (lane < 32) {
             const int kk = lane >> 1, c = lane & 1, smk = (best8x8 >> (4 * (((kk >> 3) << 1) + ((kk & 3) >> 1)))) & 15;
-            L[4].mv[kk][c] = s.e.all_mv[smk][kk][c];
-            L[4].mvd[kk][c] = (int16_t)(s.e.all_mv[smk][kk][c] - s.pmv[smk][kk][c]);
+            P.mv[kk][c] = s.e.all_mv[smk][kk][c];
+            P.mvd[kk][c] = (int16_t)(s.e.all_mv[smk][kk][c] - s.pmv[smk][kk][c]);
         }
-        if (lane < 4) L[4].b8mode[lane] = (int8_t)((best8x8 >> (4 * lane)) & 15);
-        const int dist = wave_sum(e2);
-        if (lane == 0) { L[4].cbp = zero ? 0 : p8cbp; L[4].cbp_blk = zero ? 0 : p8blk; L[4].dist = dist; L[4].i16mode = 0; }
+        if (lane < 4) P.b8mode[lane] = (int8_t)((best8x8 >> (4 * lane)) & 15);
+        rdo_luma_close(P, zero ? s.p8pred : s.p8rec, s.e.org, zero ? 0 : p8cbp, zero ? 0 : p8blk, lane);
     }
     // ---- FindSkipModeMotionVector [J] (wave-uniform), the spatial memory of the next MB (its EPZS
     //      predictor 34)
@@ -593,26 +629,26 @@ __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> 
     // ---- the skip / 16x16 / 16x8 / 8x16 candidates (LumaResidualCoding) and the chroma of all five
     //      (ChromaResidualCoding [J], the MC of each candidate's MVs)
 #pragma unroll 1
-    for (int c = 0; c < 5; c++) {
-        if (c == 4 ? !p8 : c > 0 && !inter_on(d.isr, c)) continue;   // uniform
+    for (int c = RD_SKIP; c <= RD_P8x8; c++) {
+        if (c == RD_P8x8 ? !p8 : c > 0 && !inter_on(d.isr, c)) continue;   // uniform
         if (lane < 32) {
             const int k = lane >> 1, cc = lane & 1;
             const int smk = (best8x8 >> (4 * (((k >> 3) << 1) + ((k & 3) >> 1)))) & 15;
-            const int v = c == 0 ? (cc ? skipy : skipx) : s.e.all_mv[c == 4 ? smk : c][k][cc];
+            const int v = c == RD_SKIP ? (cc ? skipy : skipx) : s.e.all_mv[c == RD_P8x8 ? smk : c][k][cc];
             s.fmv[k][cc] = (int16_t)v;
-            if (c < 4) {
+            if (c < RD_P8x8) {
                 L[c].mv[k][cc] = (int16_t)v;
-                L[c].mvd[k][cc] = (int16_t)(c == 0 ? 0 : v - s.pmv[c][k][cc]);
+                L[c].mvd[k][cc] = (int16_t)(c == RD_SKIP ? 0 : v - s.pmv[c][k][cc]);
             }
         }
-        if (c < 4 && lane < 4) L[c].b8mode[lane] = (int8_t)c;
+        if (c < RD_P8x8 && lane < 4) L[c].b8mode[lane] = (int8_t)c;
         wave_lds_sync();
-        if (c < 4) luma_inter(d, s, wn, &L[c], c == 0, mbx, mby, lane);
+        if (c < RD_P8x8) luma_inter(d, s, wn, &L[c], c == RD_SKIP, mbx, mby, lane);
         // the MB's chroma source straight from the picture (each sample read once per candidate;
         // 128-256 B less LDS, profiles/r7n_rdo_lds_ab.txt)
         const int ostr = d.Wc;
         const pel *oc0 = spl<pel>(d.orgU) + 8 * mby * ostr + 8 * mbx, *oc1 = spl<pel>(d.orgV) + 8 * mby * ostr + 8 * mbx;
-        const int dist = chroma_cand_w<pel>(d, oc0, oc1, ostr, nullptr, 0, s.fmv, c == 0, &scr->C[c], lane, mbx, mby, mav.T, mav.L);
+        const int dist = chroma_cand_w<pel>(d, oc0, oc1, ostr, nullptr, 0, s.fmv, c == RD_SKIP, &scr->C[c], lane, mbx, mby, mav.T, mav.L);
         if (lane == 0) scr->C[c].dist = dist;
         wave_lds_sync();
     }
@@ -620,18 +656,19 @@ __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> 
     //      the P8x8 whose four blocks chose the 8x8 sub-mode; the chroma is the base candidate's
     if constexpr (T8) {
 #pragma unroll 1
-        for (int c = 1; c <= 4; c++) {
-            if (c == 4 ? !(p8 && best8x8 == 0x4444) : !inter_on(d.isr, c)) continue;   // uniform
+        for (int c = RD_16x16; c <= RD_P8x8; c++) {     // the block type c of the searches, all sub-modes 8x8 for P8x8
+            if (c == RD_P8x8 ? !(p8 && best8x8 == 0x4444) : !inter_on(d.isr, c)) continue;   // uniform
+            RdoLuma<pel> &L8 = L[rd_with_t8(c)];
             if (lane < 32) {
-                const int k = lane >> 1, cc = lane & 1, sm = c == 4 ? 4 : c;
-                const int v = s.e.all_mv[sm][k][cc];
+                const int k = lane >> 1, cc = lane & 1;
+                const int v = s.e.all_mv[c][k][cc];
                 s.fmv[k][cc] = (int16_t)v;
-                L[c + 7].mv[k][cc] = (int16_t)v;
-                L[c + 7].mvd[k][cc] = (int16_t)(v - s.pmv[sm][k][cc]);
+                L8.mv[k][cc] = (int16_t)v;
+                L8.mvd[k][cc] = (int16_t)(v - s.pmv[c][k][cc]);
             }
-            if (lane < 4) L[c + 7].b8mode[lane] = (int8_t)(c == 4 ? 4 : c);
+            if (lane < 4) L8.b8mode[lane] = (int8_t)c;
             wave_lds_sync();
-            luma_inter8(d, s, wn, &L[c + 7], mbx, mby, lane);
+            luma_inter8(d, s, wn, &L8, mbx, mby, lane);
             wave_lds_sync();
         }
     }
@@ -646,7 +683,7 @@ __device__ __forceinline__ void rdo_inter_mb(const DevParams &d, RdoInterS<pel> 
 template <class pel, bool T8>
 struct RdoI8S {
     alignas(4) pel rec8[256];     // the Intra8x8 reconstruction in progress
-    int raw[25], av[25], f[25];   // the reference edge: [7 - y] left, [8] corner, [9 + x] top (8.3.2.2.1)
+    I8Edge e;                     // the block's reference edge
     int16_t lev8[9][64];          // per mode: levels in 8x8 zig-zag order
     alignas(4) pel r8[9][64];     // per mode: the block's reconstruction (raster)
     int m8[4];                    // the decided modes
@@ -674,13 +711,6 @@ struct RdoIntraS {
     int16_t dclev[16];
 };
 
-template <class pel, bool T8>
-__device__ __forceinline__ int i4_lpix(const RdoIntraS<pel, T8> &s, int x, int y) {
-    if (y < 0) return s.nb.rtop[x + 1];
-    if (x < 0) return s.nb.rleft[y];
-    return s.rec[16 * y + x];
-}
-
 // Intra8x8 (Transform8x8Mode, item 63): Mode_Decision_for_8x8IntraBlocks [J] by RDCost_for_8x8IntraBlocks,
 // the four blocks in order on one wave: the filtered reference edge (8.3.2.2.1), a pass per mode
 // (lane = sample: prediction, dct_luma8x8, reconstruction, SSD), lane m rates mode m from the
@@ -696,44 +726,24 @@ __device__ __forceinline__ void rdo_intra8(const DevParams &d, RdoIntraS<pel, tr
 #pragma unroll 1
     for (int b8 = 0; b8 < 4; b8++) {
         const int bx = 8 * (b8 & 1), by = 8 * (b8 >> 1);
+        // i8_avail (jmh_intra.h), spelled out: through the call the CAVLC instantiations' VGPRs move
         const bool left = bx ? true : mav.L, up = by ? true : mav.T;
         const bool ul = bx && by ? true : bx ? mav.T : by ? mav.L : mav.TL;
-        const bool ur = b8 == 0 ? mav.T : b8 == 1 ? mav.TR : b8 == 2;
-        if (lane < 25) {
-            int xm, ym;
-            bool av;
-            if (lane < 8) { xm = bx - 1; ym = by + 7 - lane; av = left; }
-            else if (lane == 8) { xm = bx - 1; ym = by - 1; av = ul; }
-            else { const int xx = lane - 9; xm = bx + (xx < 8 || ur ? xx : 7); ym = by - 1; av = up; }
-            int v = 0;
-            if (av) v = (xm >= 0 && xm < 16 && ym >= 0) ? q.rec8[ym * 16 + xm] : recY[(pix_y + ym) * W + pix_x + xm];
-            q.raw[lane] = v;
-            q.av[lane] = av;
-        }
-        for (int k = lane; k < 9 * (JMR_NCTX / 4) && !CAV; k += 64) {   // each rate lane's copy of the MB-start state
-            const int m = k / (JMR_NCTX / 4), j = k - m * (JMR_NCTX / 4);
-            reinterpret_cast<uint32_t *>(s.stc[m])[j] = reinterpret_cast<const uint32_t *>(s.st0)[j];
-        }
+        const BlkAvail nbv{up, left, ul, b8 == 0 ? mav.T : b8 == 1 ? mav.TR : b8 == 2};
+        i8_edge_load(q.e, lane, b8, nbv, q.rec8, recY, pix_x, pix_y, W);
+        if (!CAV) rdo_state_fan(s.stc, s.st0, 9, lane, 64);   // the MB-start state
         wave_lds_sync();
-        if (lane < 25 && q.av[lane]) {
-            const int c = q.raw[lane];
-            const int lo = lane > 0 && q.av[lane - 1] ? q.raw[lane - 1] : c, hi = lane < 24 && q.av[lane + 1] ? q.raw[lane + 1] : c;
-            q.f[lane] = (lo + 2 * c + hi + 2) >> 2;
-        }
+        i8_edge_filter(q.e, lane);
         // predIntra8x8PredMode (8.3.2.1): this MB's earlier blocks, else the neighbour's 4x4 mode
         const int ma = bx ? q.m8[b8 - 1] : s.bd.ipm[6 + (by >> 2)], mb = by ? q.m8[b8 - 2] : s.bd.ipm[1 + (bx >> 2)];
-        const int mpm = (ma < 0 || mb < 0) ? 2 : min(ma, mb);
+        const int mpm = intra_mpm(ma, mb);
         wave_lds_sync();
-        int st = 0, sl = 0;
-        for (int i = 0; i < 8; i++) { st += up ? q.f[9 + i] : 0; sl += left ? q.f[i] : 0; }
-        const int dcv = up && left ? (st + sl + 8) >> 4 : up ? (st + 4) >> 3 : left ? (sl + 4) >> 3 : (maxv + 1) >> 1;
+        const int dcv = i8_edge_dc(q.e, up, left, maxv);
         const int ov = s.org[(by + y) * 16 + bx + x];
 #pragma unroll 1
         for (int m = 0; m < 9; m++) {                   // the nine modes' dct_luma8x8 (wave-uniform skips)
-            const bool ok = m == 2 || ((m == 0 || m == 3 || m == 7) && up) || ((m == 1 || m == 8) && left) ||
-                            ((m == 4 || m == 5 || m == 6) && up && left && ul);
-            if (!ok) continue;
-            const int p = i8_pred_px(q.f, dcv, m, x, y);
+            if (!intra_mode_ok(m, up, left, ul)) continue;
+            const int p = i8_pred_px(q.e.f, dcv, m, x, y);
             const int c = wave_fwd8x8(ov - p, lane);
             int lev, dq, cost;
             const unsigned long long nz = wave_quant8(c, lane, qp, rnd, lev, dq, cost);
@@ -746,52 +756,36 @@ __device__ __forceinline__ void rdo_intra8(const DevParams &d, RdoIntraS<pel, tr
         wave_lds_sync();
         {                                               // lane m: the block's rate in mode m
             const int m = lane;
-            const bool ok = m < 9 && (m == 2 || ((m == 0 || m == 3 || m == 7) && up) || ((m == 1 || m == 8) && left) ||
-                                      ((m == 4 || m == 5 || m == 6) && up && left && ul));
-            if (ok && CAV) s.bits[m] = jmv_i8(A, B, s.tcd, b8, m == mpm ? -1 : m < mpm ? m : m - 1, q.lev8[m], s.tcm[m]);
+            const bool ok = m < 9 && intra_mode_ok(m, up, left, ul);
+            if (ok && CAV) s.bits[m] = jmv_i8(A, B, s.tcd, b8, intra_rem(m, mpm), q.lev8[m], s.tcm[m]);
             else if (ok) {
                 jmr_eng e = {s.stc[m], rg0, 0};
-                jmr_i8(&e, m == mpm ? -1 : m < mpm ? m : m - 1, q.lev8[m]);
+                jmr_i8(&e, intra_rem(m, mpm), q.lev8[m]);
                 s.bits[m] = e.bits;
             }
         }
         wave_lds_sync();
-        double best = 1e30;                             // wave-uniform decision, strict '<'
-        int bm = 2;
-        for (int mm = 0; mm < 9; mm++) {
-            const bool ok = mm == 2 || ((mm == 0 || mm == 3 || mm == 7) && up) || ((mm == 1 || mm == 8) && left) ||
-                            ((mm == 4 || mm == 5 || mm == 6) && up && left && ul);
-            if (!ok) continue;
-            const double rd = rd_cost(s.dist[mm], s.bits[mm], d.lambda_rd);
-            if (rd < best) { best = rd; bm = mm; }
-        }
+        const int bm = rd_argmin(s.dist, s.bits, 9, d.lambda_rd, 2, [=](int m) { return intra_mode_ok(m, up, left, ul); });   // wave-uniform
         q.rec8[(by + y) * 16 + bx + x] = q.r8[bm][lane];
         L.luma[il_blk(b8, lane)][lane >> 2] = q.lev8[bm][lane];
         if (lane == 0) {
             q.m8[b8] = bm;
-            L.ipm[(b8 >> 1) * 8 + (b8 & 1) * 2] = (int8_t)(bm == mpm ? -1 : bm < mpm ? bm : bm - 1);
+            L.ipm[(b8 >> 1) * 8 + (b8 & 1) * 2] = (int8_t)intra_rem(bm, mpm);
         }
         if (lane < 4) s.tcd[((b8 >> 1) * 2 + (lane >> 1)) * 4 + (b8 & 1) * 2 + (lane & 1)] = s.tcm[bm][lane];
         if (s.nz[bm]) { cbp |= 1 << b8; blkm |= 0x33 << ((b8 >> 1) * 8 + (b8 & 1) * 2); }
         wave_lds_sync();
     }
-    int e2 = 0;
-    for (int i = lane; i < 256; i += 64) {
-        L.rec[i] = q.rec8[i];
-        const int e = (int)s.org[i] - (int)q.rec8[i];
-        e2 += e * e;
-    }
     if (lane < 16) L.imode[lane] = (int8_t)q.m8[((lane >> 3) << 1) + ((lane & 3) >> 1)];
     if (lane < 32) L.mv[lane >> 1][lane & 1] = 0;
-    const int dist = wave_sum(e2);
-    if (lane == 0) { L.cbp = cbp; L.cbp_blk = blkm; L.dist = dist; L.i16mode = 0; }
+    rdo_luma_close(L, q.rec8, s.org, cbp, blkm, lane);
 }
 
 template <class pel, bool T8, bool CAV>
 __device__ __forceinline__ void rdo_intra_mb(const DevParams &d, RdoIntraS<pel, T8> &s, RdoScr<pel> *scr, int mbx, int mby, int lane) {
     const int a = mby * d.mbw + mbx, W = d.W, pix_x = 16 * mbx, pix_y = 16 * mby, qp = d.qp + d.qpbd, maxv = d.maxv;
-    const MbAvail mav0 = mb_avail(d, mbx, mby), mav = intra_avail(d, mbx, mby);   // context neighbours / intra prediction
-    const bool avL = mav.L, avT = mav.T, avTL = mav.TL, avTR = mav.TR;
+    const MbAvail mav0 = mb_avail(d, mbx, mby), mav = intra_avail(d, mbx, mby);
+    const bool avL = mav.L, avT = mav.T, avTL = mav.TL;
     const bool prof = d.prof && lane == 0 && d.prof_mb == a;   // debug (JMH_PHASE_PROF): stamps 53..56
     PSTAMP(53);
     const pel *orgY = spl<pel>(d.orgY);
@@ -801,13 +795,7 @@ __device__ __forceinline__ void rdo_intra_mb(const DevParams &d, RdoIntraS<pel, 
     if (lane >= 54 && lane < 64) load_border(d, s.bd, lane - 54, mbx, mby);
     const uint32_t rg0 = rdo_state_load(d, a, s.st0, lane, 64);
     jmr_lds_tables_load(lane, 64);
-    {
-        const int nw = (int)sizeof(jmr_mbinfo) / 4;
-        if (lane < nw) {
-            if (mav0.L) reinterpret_cast<uint32_t *>(&s.nbA)[lane] = reinterpret_cast<const uint32_t *>(d.rp->mbi + a - 1)[lane];
-            if (mav0.T) reinterpret_cast<uint32_t *>(&s.nbB)[lane] = reinterpret_cast<const uint32_t *>(d.rp->mbi + a - d.mbw)[lane];
-        }
-    }
+    rdo_nb_load(d, a, mav0, s.nbA, s.nbB, lane);
     wave_lds_sync();
     const jmr_mbinfo *A = mav0.L ? &s.nbA : nullptr, *B = mav0.T ? &s.nbB : nullptr;
     RdoLuma<pel> *L = scr->L;
@@ -840,26 +828,25 @@ __device__ __forceinline__ void rdo_intra_mb(const DevParams &d, RdoIntraS<pel, 
             const unsigned nz = lane_quant(c[i], l, qp, rnd, true, lev, dq, cc);
             if (l == 0) dq = s.dcdq[blk];
             const int rv = lane_inv4x4(dq, l, pr[i], maxv);
-            L[5].luma[blk][l] = (int16_t)lev;
-            L[5].rec[py4 * 16 + px4] = (pel)rv;
+            L[RD_I16].luma[blk][l] = (int16_t)lev;
+            L[RD_I16].rec[py4 * 16 + px4] = (pel)rv;
             e2 += (o[i] - rv) * (o[i] - rv);
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 if (__builtin_amdgcn_readlane((int)nz, 16 * q)) { cbp = 15; blkm |= 1 << (4 * i + q); }
         }
-        if (lane < 16) L[5].luma_dc[lane] = s.dclev[lane];
-        if (lane < 32) L[5].mv[lane >> 1][lane & 1] = 0;
+        if (lane < 16) L[RD_I16].luma_dc[lane] = s.dclev[lane];
+        if (lane < 32) L[RD_I16].mv[lane >> 1][lane & 1] = 0;
         const int dist = wave_sum(e2);
-        if (lane == 0) { L[5].cbp = cbp; L[5].cbp_blk = blkm; L[5].dist = dist; L[5].i16mode = m16; }
+        if (lane == 0) { L[RD_I16].cbp = cbp; L[RD_I16].cbp_blk = blkm; L[RD_I16].dist = dist; L[RD_I16].i16mode = m16; }
     }
     PSTAMP(54);
     // ---- the four chroma intra modes (ChromaResidualCoding of IntraChromaPrediction8x8 [J])
 #pragma unroll 1
     for (int m = 0; m < 4; m++) {
-        const bool act = m == 0 || (m == 1 ? avL : m == 2 ? avT : avT && avL && avTL);
-        if (!act) continue;                             // uniform
-        const int dist = chroma_cand_w<pel>(d, s.nb.orgc[0], s.nb.orgc[1], 8, &s.nb, m, nullptr, false, &scr->C[5 + m], lane, mbx, mby, avT, avL);
-        if (lane == 0) scr->C[5 + m].dist = dist;
+        if (!chroma_mode_ok(m, avL, avT, avTL)) continue;   // uniform
+        const int dist = chroma_cand_w<pel>(d, s.nb.orgc[0], s.nb.orgc[1], 8, &s.nb, m, nullptr, false, &scr->C[rd_cintra(m)], lane, mbx, mby, avT, avL);
+        if (lane == 0) scr->C[rd_cintra(m)].dist = dist;
     }
     // ---- Intra4x4: Mode_Decision_for_4x4IntraBlocks [J] by RDCost_for_4x4IntraBlocks, 16 blocks in
     //      coding order: 9 modes x 16 lanes code (three passes), lane m rates mode m, a wave-uniform
@@ -875,25 +862,20 @@ __device__ __forceinline__ void rdo_intra_mb(const DevParams &d, RdoIntraS<pel, 
     for (int i = 0; i < 16; i++) {
         const int b8 = i >> 2, bb = i & 3;
         const int bx = 8 * (b8 & 1) + 4 * (bb & 1), by = 8 * (b8 >> 1) + 4 * (bb >> 1), bx4 = bx >> 2, by4 = by >> 2, blk = 4 * by4 + bx4;
-        const bool up = by > 0 || avT, left = bx > 0 || avL;
-        const bool ul = (bx > 0 && by > 0) || (bx == 0 && by > 0 && avL) || (bx > 0 && by == 0 && avT) || (bx == 0 && by == 0 && avTL);
-        bool ur = by == 0 ? (bx + 4 <= 15 ? avT : avTR) : (bx + 4 <= 15);
-        if ((bx == 4 || bx == 12) && (by == 4 || by == 12)) ur = false;
+        const BlkAvail nbv = i4_avail(bx, by, mav);
+        const bool up = nbv.up, left = nbv.left, ul = nbv.ul, ur = nbv.ur;
         if (lane < 13) {
             int v;
-            if (lane == 0) v = ul ? i4_lpix(s, bx - 1, by - 1) : 0;
-            else if (lane <= 4) v = up ? i4_lpix(s, bx + lane - 1, by - 1) : 0;
-            else if (lane <= 8) v = up ? i4_lpix(s, ur ? bx + lane - 1 : bx + 3, by - 1) : 0;
-            else v = left ? i4_lpix(s, bx - 1, by + lane - 9) : 0;
+            if (lane == 0) v = ul ? lpix(s, bx - 1, by - 1) : 0;
+            else if (lane <= 4) v = up ? lpix(s, bx + lane - 1, by - 1) : 0;
+            else if (lane <= 8) v = up ? lpix(s, ur ? bx + lane - 1 : bx + 3, by - 1) : 0;
+            else v = left ? lpix(s, bx - 1, by + lane - 9) : 0;
             s.P[lane] = v;
         }
         const int upM = by > 0 ? s.ipred_cur[blk - 4] : s.bd.ipm[1 + bx4];
         const int leftM = bx > 0 ? s.ipred_cur[blk - 1] : s.bd.ipm[6 + by4];
-        const int mpm = (upM < 0 || leftM < 0) ? 2 : min(upM, leftM);
-        for (int k = lane; k < 9 * (JMR_NCTX / 4) && !CAV; k += 64) {   // each rate lane's copy of the MB-start state
-            const int m = k / (JMR_NCTX / 4), j = k - m * (JMR_NCTX / 4);
-            reinterpret_cast<uint32_t *>(s.stc[m])[j] = reinterpret_cast<const uint32_t *>(s.st0)[j];
-        }
+        const int mpm = (upM < 0 || leftM < 0) ? 2 : min(upM, leftM);   // intra_mpm (its call here costs k_rdo_intra<., false, true> 4 VGPRs)
+        if (!CAV) rdo_state_fan(s.stc, s.st0, 9, lane, 64);   // the MB-start state
         wave_lds_sync();
         const int org = s.org[(by + (l >> 2)) * 16 + bx + (l & 3)];
         const int st = s.P[1] + s.P[2] + s.P[3] + s.P[4], sl = s.P[9] + s.P[10] + s.P[11] + s.P[12];
@@ -917,86 +899,57 @@ __device__ __forceinline__ void rdo_intra_mb(const DevParams &d, RdoIntraS<pel, 
         wave_lds_sync();
         {                                               // lane m: the block's rate in mode m
             const int m = lane;
-            const bool avm = m < 9 && (m == 2 || ((m == 0 || m == 3 || m == 7) && up) || ((m == 1 || m == 8) && left) || (up && left && ul));
+            const bool avm = m < 9 && intra_mode_ok(m, up, left, ul);
             if (avm && CAV) {
                 int tc;
-                s.bits[m] = jmv_i4(A, B, s.tcd, bx4, by4, m == mpm ? -1 : m < mpm ? m : m - 1, s.lev[m], &tc);
+                s.bits[m] = jmv_i4(A, B, s.tcd, bx4, by4, intra_rem(m, mpm), s.lev[m], &tc);
                 s.tcm[m][0] = (uint8_t)tc;
             } else if (avm) {
                 jmr_eng e = {s.stc[m], rg0, 0};
-                jmr_i4(&e, A, B, bx4, by4, m == mpm ? -1 : m < mpm ? m : m - 1, s.lev[m]);
+                jmr_i4(&e, A, B, bx4, by4, intra_rem(m, mpm), s.lev[m]);
                 s.bits[m] = e.bits;
             }
         }
         wave_lds_sync();
-        double best = 1e30;                             // wave-uniform decision, strict '<'
-        int bm = 2;
-        for (int mm = 0; mm < 9; mm++) {
-            const bool av = mm == 2 || ((mm == 0 || mm == 3 || mm == 7) && up) || ((mm == 1 || mm == 8) && left) || (up && left && ul);
-            if (!av) continue;
-            const double rd = rd_cost(s.dist[mm], s.bits[mm], d.lambda_rd);
-            if (rd < best) { best = rd; bm = mm; }
-        }
+        const int bm = rd_argmin(s.dist, s.bits, 9, d.lambda_rd, 2, [=](int m) { return intra_mode_ok(m, up, left, ul); });   // wave-uniform
         if (lane == 0) {
             s.tcd[blk] = s.tcm[bm][0];
             s.ipred_cur[blk] = (int8_t)bm;
-            L[6].imode[blk] = (int8_t)bm;
-            L[6].ipm[blk] = (int8_t)(bm == mpm ? -1 : bm < mpm ? bm : bm - 1);
+            L[RD_I4].imode[blk] = (int8_t)bm;
+            L[RD_I4].ipm[blk] = (int8_t)intra_rem(bm, mpm);
         }
         if (s.nz[bm]) { i4cbp |= 1 << b8; i4blk |= 1 << blk; }
         if (lane < 16) {
             s.rec[(by + (lane >> 2)) * 16 + bx + (lane & 3)] = s.r4[bm][lane];
-            L[6].luma[blk][lane] = s.lev[bm][lane];
+            L[RD_I4].luma[blk][lane] = s.lev[bm][lane];
         }
         wave_lds_sync();
     }
-    int e2 = 0;
-    for (int i = lane; i < 256; i += 64) {
-        L[6].rec[i] = s.rec[i];
-        const int e = (int)s.org[i] - (int)s.rec[i];
-        e2 += e * e;
-    }
-    const int dist = wave_sum(e2);
-    if (lane == 0) { L[6].cbp = i4cbp; L[6].cbp_blk = i4blk; L[6].dist = dist; L[6].i16mode = 0; }
-    if (lane < 32) L[6].mv[lane >> 1][lane & 1] = 0;
+    rdo_luma_close(L[RD_I4], s.rec, s.org, i4cbp, i4blk, lane);
+    if (lane < 32) L[RD_I4].mv[lane >> 1][lane & 1] = 0;
     if constexpr (T8) {
         if (lane < 24) s.tcd[lane] = 0;
         wave_lds_sync();
-        rdo_intra8<pel, CAV>(d, s, L[7], A, B, rg0, mav, mbx, mby, lane);
+        rdo_intra8<pel, CAV>(d, s, L[RD_I8], A, B, rg0, mav, mbx, mby, lane);
     }
     PSTAMP(56);
     // ---- RDCost_for_macroblocks' rate of the eight intra candidates (I16MB / I4MB x the chroma
     //      modes; Transform8x8Mode: and I8MB), here beside k_rdo_inter rather than on k_rdo_final's
     //      critical path: lane k < 8 (12) codes candidate k on its own copy of the slice state (the
     //      Intra4x4 copies, free now), reading the candidates this wave wrote to the tick scratch
-    constexpr int NI = T8 ? 12 : 8;
+    constexpr int NI = 4 * (T8 ? RD_NINTRA : RD_NINTRA - 1);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    for (int k = lane; k < NI * (JMR_NCTX / 4) && !CAV; k += 64) {
-        const int m = k / (JMR_NCTX / 4), j = k - m * (JMR_NCTX / 4);
-        reinterpret_cast<uint32_t *>(s.stc[m])[j] = reinterpret_cast<const uint32_t *>(s.st0)[j];
-    }
+    if (!CAV) rdo_state_fan(s.stc, s.st0, NI, lane, 64);
     wave_lds_sync();
-    const int cm = lane & 3;
-    const bool cok = cm == 0 || (cm == 1 ? avL : cm == 2 ? avT : avT && avL && avTL);
-    if (lane < NI && cok) {
-        const RdoLuma<pel> &Lc = L[5 + (lane >> 2)];
-        const RdoChroma<pel> &C = scr->C[5 + cm];
+    const int ci = RD_I16 + (lane >> 2), cm = lane & 3;     // lane = rd_rslot(ci, cm)
+    if (lane < NI && chroma_mode_ok(cm, avL, avT, avTL)) {
+        const RdoLuma<pel> &Lc = L[ci];
+        const RdoChroma<pel> &C = scr->C[rd_cintra(cm)];
         RdoRate &R = scr->R[lane];
         jmr_cand r;
-        r.mb_type = lane < 4 ? JMH_I16MB : lane < 8 ? JMH_I4MB : JMH_I8MB;
-        r.cbp = Lc.cbp | C.cbpc << 4;
-        r.i16mode = Lc.i16mode;
-        r.cmode = cm;
-        r.t8 = lane >= 8;
-        for (int q = 0; q < 4; q++) r.b8mode[q] = 0;
-        r.ipm = Lc.ipm;
-        r.mvd = Lc.mvd;
-        r.luma = Lc.luma;
-        r.luma_dc = Lc.luma_dc;
-        r.cdc = C.dc;
-        r.cac = C.ac;
-        r.mvw = R.mvw;
+        // (rd_mb_type(ci), spelled out: its call moves four instantiations' VGPRs)
+        rdo_cand_fill(r, ci == RD_I16 ? JMH_I16MB : ci == RD_I4 ? JMH_I4MB : JMH_I8MB, Lc, C, cm, rd_t8(ci), nullptr, Lc, C, R.mvw);
         if (CAV) {                                  // rg0: the mb_skip_run before this macroblock
             R.bits = jmv_mb(A, B, &r, d.slice_type == JMH_P_SLICE, T8, (int)rg0, reinterpret_cast<uint8_t *>(R.mvw), &R.out);
             R.range = 0;
@@ -1073,12 +1026,13 @@ struct RdoFinC {                  // of a chroma candidate (RdoChroma's first 27
     int16_t dc[2][4];
     int16_t ac[2][4][16];
 };
-// the inter candidates' LDS syntax slot: 0..4 and (Transform8x8Mode) 8..11 -> 5..8
-__device__ __forceinline__ int rd_fslot(int i) { return i < 5 ? i : i - 3; }
+// the inter candidates' LDS syntax slot: the five bases, then their 8x8-transform twins
+__device__ __forceinline__ int rd_fslot(int i) { return i < RD_NBASE ? i : i - RD_NINTRA; }
+__device__ __forceinline__ int rd_fslot_cand(int f) { return f < RD_NBASE ? f : f + RD_NINTRA; }   // its inverse
 template <class pel>
 struct RdoFinS {
-    RdoFinL fl[9];                // the inter candidates' syntax in LDS: the serial CABAC loops read it bin by bin
-    RdoFinC fc[5];
+    RdoFinL fl[2 * RD_NBASE - 1];   // the inter candidates' syntax in LDS: the serial CABAC loops read it bin by bin
+    RdoFinC fc[RD_NBASE];
     int16_t mvw[RD_NCAND][16][2];   // jmr_mb's work buffers
     alignas(4) uint8_t st0[JMR_NCTX];
     alignas(4) uint8_t stc[RD_NCAND][JMR_NCTX];
@@ -1119,22 +1073,26 @@ __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(co
     if (tid < 64) {
         const uint32_t rg = rdo_state_load(d, a, s.st0, tid, 64);
         if (tid == 0) s.rg0 = rg;
-    } else if (tid < 128) rdo_nb_load(d, mbx, mby, s.nbA, s.nbB, s.hasA, s.hasB, tid - 64);
+    } else if (tid < 128) {
+        const MbAvail nav = mb_avail(d, mbx, mby);
+        rdo_nb_load(d, a, nav, s.nbA, s.nbB, tid - 64);
+        if (tid == 64) { s.hasA = nav.L; s.hasB = nav.T; }
+    }
     else if (tid >= 160) jmr_lds_tables_load(tid - 160, 96);
     else if (tid == 128) {                              // the candidates in JM's order (item 63 with Transform8x8Mode)
         const bool p8 = inter_on(d.isr, 4) || inter_on(d.isr, 5) || inter_on(d.isr, 6) || inter_on(d.isr, 7);
-        const bool p8t8 = T8 && p8 && scr->L[4].b8mode[0] == 4 && scr->L[4].b8mode[1] == 4 && scr->L[4].b8mode[2] == 4 &&
-                          scr->L[4].b8mode[3] == 4;
-        const bool cav[4] = {true, mav.L, mav.T, mav.T && mav.L && mav.TL};
-        static constexpr int8_t order[RD_NL] = {0, 1, 8, 2, 9, 3, 10, 4, 11, 5, 6, 7};
+        const int8_t *pm = scr->L[RD_P8x8].b8mode;
+        const bool p8t8 = T8 && p8 && pm[0] == 4 && pm[1] == 4 && pm[2] == 4 && pm[3] == 4;
+        static constexpr int8_t order[RD_NL] = {RD_SKIP, RD_16x16, RD_16x16_T8, RD_16x8, RD_16x8_T8, RD_8x16, RD_8x16_T8, RD_P8x8, RD_P8x8_T8,
+                                                RD_I16, RD_I4, RD_I8};
         int n = 0;
         for (int cm = 0; cm < 4; cm++) {
-            if (!cav[cm]) continue;
+            if (!chroma_mode_ok(cm, mav.L, mav.T, mav.TL)) continue;
             for (int oi = 0; oi < RD_NL; oi++) {
                 const int i = order[oi], b = rd_cbase(i);
-                const bool intra = i >= 5 && i <= 7;
-                bool valid = intra ? (i < 7 || T8) : slice_p && (b == 0 || (b == 4 ? p8 : inter_on(d.isr, b)));
-                if (i >= 8) valid = valid && T8 && (i != 11 || p8t8);
+                const bool intra = rd_is_intra(i);
+                bool valid = intra ? (i != RD_I8 || T8) : slice_p && (b == RD_SKIP || (b == RD_P8x8 ? p8 : inter_on(d.isr, b)));
+                if (i >= RD_16x16_T8) valid = valid && T8 && (i != RD_P8x8_T8 || p8t8);
                 if (!valid || (cm != 0 && !intra)) continue;
                 s.ci[n] = i; s.ccm[n] = cm; n++;
             }
@@ -1147,8 +1105,8 @@ __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(co
         for (int w = 0; w < 16; w++) s.kof[w >> 2][w & 3] = -1;
         for (int k = 0; k < n; k++) {
             const int i = s.ci[k], b = rd_cbase(i);
-            if (i >= 5 && i <= 7) continue;
-            const int w = b == 1 ? 0 : b == 2 ? 1 : b == 4 ? 3 : 2;
+            if (rd_is_intra(i)) continue;
+            const int w = b == RD_16x16 ? 0 : b == RD_16x8 ? 1 : b == RD_P8x8 ? 3 : 2;
             s.kof[w][fill[w]++] = (int8_t)k;
         }
     }
@@ -1158,18 +1116,18 @@ __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(co
     //      four waves, grouped by macroblock type: kof)
     for (int i = tid; i < s.ncand * (JMR_NCTX / 4) && !CAV; i += NT) {   // the inter candidates' state copies
         const int k = i / (JMR_NCTX / 4), j = i - k * (JMR_NCTX / 4), ci = s.ci[k];
-        if (ci < 5 || ci >= 8) reinterpret_cast<uint32_t *>(s.stc[k])[j] = reinterpret_cast<const uint32_t *>(s.st0)[j];
+        if (!rd_is_intra(ci)) reinterpret_cast<uint32_t *>(s.stc[k])[j] = reinterpret_cast<const uint32_t *>(s.st0)[j];
     }
     {
         constexpr int nl = 672 / 4, nc = (int)sizeof(RdoFinC) / 4;
         static_assert(offsetof(RdoLuma<pel>, ipm) > 672 && offsetof(RdoFinL, ipm) == 672, "RdoFinL layout");
-        const int nfl = T8 ? 9 : 5;
+        const int nfl = T8 ? 2 * RD_NBASE - 1 : RD_NBASE;   // no 8x8-transform P_Skip
         for (int i = tid; i < nfl * (nl + 4); i += NT) {
-            const int f = i / (nl + 4), j = i - f * (nl + 4), k = f < 5 ? f : f + 3;
+            const int f = i / (nl + 4), j = i - f * (nl + 4), k = rd_fslot_cand(f);
             const uint32_t *src = reinterpret_cast<const uint32_t *>(&scr->L[k]);
             reinterpret_cast<uint32_t *>(&s.fl[f])[j] = j < nl ? src[j] : reinterpret_cast<const uint32_t *>(scr->L[k].ipm)[j - nl];
         }
-        for (int i = tid; i < 5 * nc; i += NT) {
+        for (int i = tid; i < RD_NBASE * nc; i += NT) {
             const int k = i / nc, j = i - k * nc;
             reinterpret_cast<uint32_t *>(&s.fc[k])[j] = reinterpret_cast<const uint32_t *>(&scr->C[k])[j];
         }
@@ -1177,13 +1135,13 @@ __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(co
         const int nw = (int)sizeof(jmr_mbinfo) / 4;
         for (int i = tid; i < s.ncand * (nw + 2); i += NT) {
             const int k = i / (nw + 2), j = i - k * (nw + 2), ci = s.ci[k];
-            if (ci < 5 || ci > 7) continue;
-            const RdoRate &R = scr->R[4 * (ci - 5) + s.ccm[k]];
+            if (!rd_is_intra(ci)) continue;
+            const RdoRate &R = scr->R[rd_rslot(ci, s.ccm[k])];
             if (j < nw) reinterpret_cast<uint32_t *>(&s.out[k])[j] = reinterpret_cast<const uint32_t *>(&R.out)[j];
             else if (j == nw) s.rgo[k] = R.range;
             else {
                 s.bits[k] = R.bits;
-                s.rd[k] = rd_cost(scr->L[ci].dist + scr->C[5 + s.ccm[k]].dist, R.bits, d.lambda_rd);
+                s.rd[k] = rd_cost(scr->L[ci].dist + scr->C[rd_cintra(s.ccm[k])].dist, R.bits, d.lambda_rd);
             }
         }
     }
@@ -1195,7 +1153,7 @@ __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(co
         const RdoLuma<pel> &L = scr->L[i];
         const RdoChroma<pel> &C = scr->C[b];
         jmr_eng en = {s.stc[kc], s.rg0, 0};
-        if (i == 0) {
+        if (i == RD_SKIP) {
             if (CAV) {                          // P_Skip: its run is written with the next coded MB (rate 0), or
                 s.out[kc] = jmr_mbinfo{};       //   by this MB when it is the picture's last (item 64(a))
                 en.bits = jmv_skip((int)s.rg0, a == d.mbw * d.mbh - 1);
@@ -1203,21 +1161,7 @@ __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(co
             else jmr_skip(&en, A, B, &s.out[kc]);
         } else {
             jmr_cand r;
-            r.mb_type = b == 4 ? JMH_P8x8 : b;
-            r.cbp = L.cbp | C.cbpc << 4;
-            r.i16mode = L.i16mode;
-            r.cmode = 0;
-            r.t8 = T8 && i >= 8;
-            for (int q = 0; q < 4; q++) r.b8mode[q] = L.b8mode[q];
-            const RdoFinL &FL = s.fl[rd_fslot(i)];
-            const RdoFinC &FC = s.fc[b];
-            r.ipm = FL.ipm;
-            r.mvd = FL.mvd;
-            r.luma = FL.luma;
-            r.luma_dc = FL.luma_dc;
-            r.cdc = FC.dc;
-            r.cac = FC.ac;
-            r.mvw = s.mvw[kc];
+            rdo_cand_fill(r, rd_mb_type(i), L, C, 0, T8 && rd_t8(i), L.b8mode, s.fl[rd_fslot(i)], s.fc[b], s.mvw[kc]);
             if (CAV) en.bits = jmv_mb(A, B, &r, slice_p, T8, (int)s.rg0, reinterpret_cast<uint8_t *>(s.mvw[kc]), &s.out[kc]);
             else jmr_mb(&en, A, B, &r, slice_p, T8, &s.out[kc]);
         }
@@ -1238,9 +1182,9 @@ __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(co
     // ---- the chosen macroblock: results, reconstruction, picture arrays, coding state
     const int w = s.win, bi = s.ci[w], bcm = s.ccm[w], bb = rd_cbase(bi);
     const RdoLuma<pel> &L = scr->L[bi];
-    const bool is_intra = bi >= 5 && bi <= 7;
-    const RdoChroma<pel> &C = scr->C[is_intra ? 5 + bcm : bb];
-    const int mb_type = bi == 0 ? JMH_PSKIP : bb == 4 ? JMH_P8x8 : bi == 5 ? JMH_I16MB : bi == 6 ? JMH_I4MB : bi == 7 ? JMH_I8MB : bb;
+    const bool is_intra = rd_is_intra(bi);
+    const RdoChroma<pel> &C = scr->C[is_intra ? rd_cintra(bcm) : bb];
+    const int mb_type = rd_mb_type(bi);
     const int cbp = L.cbp | C.cbpc << 4, cbp_blk = L.cbp_blk;
     const bool tr8 = T8 && rd_t8(bi) && (mb_type == JMH_I8MB || (cbp & 15));   // transform_size_8x8_flag
     jmh_mb_result *res = d.res + a;
@@ -1291,12 +1235,12 @@ __global__ __launch_bounds__(NT, T8 ? JMH_RDO_FINAL_WPE : 1) void k_rdo_final(co
     {
         const int slice = a / d.slice_mbs;
         uint32_t *dst = reinterpret_cast<uint32_t *>(d.rp->cab + (size_t)slice * JMR_NCTX);
-        const uint8_t *win_ctx = is_intra ? scr->R[4 * (bi - 5) + bcm].ctx : s.stc[w];
+        const uint8_t *win_ctx = is_intra ? scr->R[rd_rslot(bi, bcm)].ctx : s.stc[w];
         if (tid < JMR_NCTX / 4 && !CAV) dst[tid] = reinterpret_cast<const uint32_t *>(win_ctx)[tid];
         const int nw = (int)sizeof(jmr_mbinfo) / 4;
         if (tid >= 128 && tid < 128 + nw)
             reinterpret_cast<uint32_t *>(d.rp->mbi + a)[tid - 128] = reinterpret_cast<const uint32_t *>(&s.out[w])[tid - 128];
-        if (tid == 192 && CAV) d.rp->range[slice] = bi == 0 ? s.rg0 + 1 : 0;   // mb_skip_run
+        if (tid == 192 && CAV) d.rp->range[slice] = bi == RD_SKIP ? s.rg0 + 1 : 0;   // mb_skip_run
         else if (tid == 192) {
             jmr_eng en = {nullptr, s.rgo[w], 0};
             if ((a + 1) % d.slice_mbs != 0 && a + 1 < d.mbw * d.mbh) jmr_end_of_mb(&en);
