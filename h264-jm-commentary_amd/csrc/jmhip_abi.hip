@@ -21,6 +21,7 @@
 #include <algorithm>
 #include "jmh_launch.h"
 #include "jmh_cavlc.h"
+#include "jmh_cabac.h"
 #include "jmh_cabac_rate.h"
 
 // quantisation rounding selector of a slice (q_round, jmh_common.h; docs/JM_SEMANTICS.md items 1
@@ -181,6 +182,7 @@ struct jmh_ctx {
     size_t fprof_n = 0;
     std::vector<uint32_t> fprof_items;
     jmh_cavlc_state *cavlc = nullptr;    // device CAVLC writer (jmh_cavlc.hip): its own stream, created on first use
+    jmh_cabac_state *cabac = nullptr;    // device CABAC writer (jmh_cabac.hip): the same
 };
 
 #define HCHK(x)                                                                  \
@@ -341,6 +343,7 @@ void jmh_destroy(jmh_ctx *c) {
     if (c->cst) (void)hipStreamSynchronize(c->cst);
     if (c->sst) (void)hipStreamSynchronize(c->sst);
     jmh_cavlc_free(c->cavlc);
+    jmh_cabac_free(c->cabac);
     for (PicBuf &b : c->ring) free_entry(b);
     void *dev_bufs[] = {c->d_ref, c->d_qpel, c->d_slots, c->d_prof, c->d_bprof, c->spic[0].cur, c->spic[0].ref, c->d_ordtab, c->spic[1].cur,
                         c->spic[1].ref, c->d_sched, c->d_soff, c->d_rscr, c->d_ffs, c->d_seg[0], c->d_seg[1], c->d_flags, c->d_head,
@@ -1123,6 +1126,23 @@ int jmh_cavlc_write_results(jmh_ctx *c, const jmh_mb_result *res, int n, const j
     if (!c || !res) return JMH_E_INVALID_ARG;
     HCHK(hipSetDevice(c->dev));
     return jmh_cavlc_run(&c->cavlc, nullptr, res, nullptr, c->mbw, c->mbh, c->cfg.transform_8x8_mode, c->cfg.constrained_intra_pred, n,
+                         slices, out, cap, where);
+}
+
+// CABAC slice data on the device (include/jmhip_cabac.h): the same stream discipline
+int jmh_cabac_write_slices(jmh_ctx *c, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap, jmh_cabac_slice_bytes *where) {
+    if (!c) return JMH_E_INVALID_ARG;
+    if (c->cur_entry < 0) return JMH_E_STATE;
+    HCHK(hipSetDevice(c->dev));
+    const PicBuf &b = c->ring[c->cur_entry];
+    return jmh_cabac_run(&c->cabac, b.res, nullptr, b.ev_done, c->mbw, c->mbh, c->cfg.transform_8x8_mode, c->cfg.constrained_intra_pred, n,
+                         slices, out, cap, where);
+}
+int jmh_cabac_write_results(jmh_ctx *c, const jmh_mb_result *res, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap,
+                            jmh_cabac_slice_bytes *where) {
+    if (!c || !res) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    return jmh_cabac_run(&c->cabac, nullptr, res, nullptr, c->mbw, c->mbh, c->cfg.transform_8x8_mode, c->cfg.constrained_intra_pred, n,
                          slices, out, cap, where);
 }
 

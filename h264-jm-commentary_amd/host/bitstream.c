@@ -515,6 +515,9 @@ void jm_slice_rate_check(const jm_slice_writer *sw, long *checked, long *bad) {
     *bad = sw ? sw->rate_bad : 0;
 }
 
+long jm_slice_bins(const jm_slice_writer *sw) { return sw ? sw->bins : 0; }
+int jm_slice_max_outstanding(const jm_slice_writer *sw) { return sw && sw->cab ? jm_cabac_max_outstanding(sw->cab) : 0; }
+
 long jm_slice_end(jm_slice_writer *sw) {
     if (!sw) return 0;
     if (sw->open) close_slice_data(sw);

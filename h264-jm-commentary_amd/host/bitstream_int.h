@@ -45,5 +45,7 @@ long jm_cabac_mb_bits(const jm_cabac *c);
 /* end_of_slice_flag = 1 of the slice's last macroblock, flush (its last bit is the
    rbsp_stop_one_bit), alignment; returns the slice's bin count */
 long jm_cabac_slice_end(jm_cabac *c);
+/* the longest run of outstanding bits PutBit resolved so far (the host reference reports it) */
+int jm_cabac_max_outstanding(const jm_cabac *c);
 
 #endif

@@ -152,6 +152,7 @@ struct jm_cabac {
     cmb *mb;
     int16_t *mvd;       /* per 4x4 of the picture [2]: mvd_l0 of the partition covering it      */
     int pending_eos;    /* a macroblock of the slice awaits its end_of_slice_flag = 0          */
+    int max_out;        /* the longest run of outstanding bits PutBit resolved (host/cabac_ref.c) */
 };
 
 jm_cabac *jm_cabac_new(const jm_seq *s) {
@@ -172,6 +173,7 @@ void jm_cabac_free(jm_cabac *c) {
 static void put_bit(jm_cabac *c, int bit) {
     if (c->first) c->first = 0;
     else jm_put(c->b, (uint32_t)bit, 1);
+    if (c->outstanding > c->max_out) c->max_out = c->outstanding;
     for (; c->outstanding > 0; c->outstanding--) jm_put(c->b, (uint32_t)(1 - bit), 1);
 }
 static void renorm(jm_cabac *c) {
@@ -371,6 +373,7 @@ void jm_cabac_write_mb(jm_cabac *c, wctx *w, int mx, int my, const jmh_mb_result
     c->mb_bits = c->nbits - nb0;
 }
 long jm_cabac_mb_bits(const jm_cabac *c) { return c->mb_bits; }
+int jm_cabac_max_outstanding(const jm_cabac *c) { return c->max_out; }
 
 static void write_mb_body(jm_cabac *c, wctx *w, int mx, int my, const jmh_mb_result *r, int slice_p) {
     const jm_seq *s = w->s;

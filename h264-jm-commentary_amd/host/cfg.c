@@ -67,6 +67,7 @@ static const map_entry Map[] = {
     {"JMCallSurface", 0, OFF(jm_call_surface), 0, 1},
     {"WriterThreads", 0, OFF(writer_threads), 0, 64},
     {"DeviceCAVLC", 0, OFF(device_cavlc), 0, 1},
+    {"DeviceCABAC", 0, OFF(device_cabac), 0, 1},
     {"JMVersion", 0, OFF(jm_version), 8, 99},
     {"QOffsetIntra", 0, OFF(qoff_intra), -1, JMH_QOFFSET_MAX},
     {"QOffsetInter", 0, OFF(qoff_inter), -1, JMH_QOFFSET_MAX},
@@ -182,7 +183,9 @@ static int parse_file(jm_input *inp, const char *fn, char *err, int errlen) {
 int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->rdopt > 1) { snprintf(err, errlen, "RDOptimization=%d not supported (0 or 1)", inp->rdopt); return -1; }
     if (inp->rdopt && inp->jm_call_surface) { snprintf(err, errlen, "JMCallSurface=1 checks the RDO-off decision (RDOptimization=0)"); return -1; }
-    if (inp->device_cavlc && inp->symbol_mode) { snprintf(err, errlen, "DeviceCAVLC=1 writes CAVLC slice data (SymbolMode=0); CABAC stays on the host"); return -1; }
+    if (inp->device_cavlc && inp->symbol_mode) { snprintf(err, errlen, "DeviceCAVLC=1 writes CAVLC slice data (SymbolMode=0); with SymbolMode=1 the device writer is DeviceCABAC=1"); return -1; }
+    if (inp->device_cabac && !inp->symbol_mode) { snprintf(err, errlen, "DeviceCABAC=1 writes CABAC slice data (SymbolMode=1); with SymbolMode=0 the device writer is DeviceCAVLC=1"); return -1; }
+    if (inp->device_cabac && inp->jm_call_surface) { snprintf(err, errlen, "DeviceCABAC=1 replaces the write_one_macroblock loop that JMCallSurface=1 runs (JMCallSurface=0)"); return -1; }
     if (inp->device_cavlc && inp->jm_call_surface) { snprintf(err, errlen, "DeviceCAVLC=1 replaces the write_one_macroblock loop that JMCallSurface=1 runs (JMCallSurface=0)"); return -1; }
     if (inp->symbol_mode && inp->profile_idc == 66) { snprintf(err, errlen, "SymbolMode=1 (CABAC) is not allowed in the Baseline profile (ProfileIDC=66)"); return -1; }
     if (inp->symbol_mode && inp->context_init_method) { snprintf(err, errlen, "ContextInitMethod=1 (adaptive CABAC model selection) not supported (0: FixedModelNumber)"); return -1; }

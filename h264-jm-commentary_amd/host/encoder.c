@@ -126,19 +126,27 @@ static int encode_picture_slices(jm86_img *im, const jm_seq *s, const jm_slice *
     return JMH_OK;
 }
 
-/* ---- DeviceCAVLC 1: image.c › code_a_picture [J] with the slice data written on the device ------
- * The slice headers are written here (jm_write_slice_header); the bits of each header's last,
- * partial byte go to the device with the slice's macroblock range, and the device returns
- * slice_data() + rbsp_trailing_bits behind them (jmh_cavlc_write_slices).  Header bytes + device
- * bytes are the slice's RBSP, wrapped by jm_write_nal as ever.  No jm_slice_write_mb, no rate
- * cross-check. */
+/* ---- DeviceCAVLC 1 / DeviceCABAC 1: image.c › code_a_picture [J] with the slice data written on
+ * the device.  The slice headers are written here (jm_write_slice_header).
+ * CAVLC: the bits of each header's last, partial byte go to the device with the slice's macroblock
+ * range, and the device returns slice_data() + rbsp_trailing_bits behind them (jmh_cavlc_write
+ * _slices).  CABAC: the header is padded with cabac_alignment_one_bits here, the device returns the
+ * coded slice_data() up to the rbsp_stop_one_bit and the slice's bins (jmh_cabac_write_slices); the
+ * cabac_zero_words rule of encode_picture_slices is then applied to the summed bins.
+ * Header bytes + device bytes are the slice's RBSP, wrapped by jm_write_nal as ever.  No
+ * jm_slice_write_mb, no writer threads, no rate cross-check. */
 static jm_cavlc_slices_fn device_cavlc_fn;
 void jm_set_device_cavlc(jm_cavlc_slices_fn fn) { device_cavlc_fn = fn; }
+static jm_cabac_slices_fn device_cabac_fn;
+void jm_set_device_cabac(jm_cabac_slices_fn fn) { device_cabac_fn = fn; }
 
 typedef struct dcavlc {
     int n;                       /* slices per picture */
+    int cabac;                   /* DeviceCABAC: cd / cwhere instead of d / where */
     jmh_slice_desc *d;
     jmh_slice_bytes *where;
+    jmh_cabac_slice_desc *cd;
+    jmh_cabac_slice_bytes *cwhere;
     jm_bits *hdr;                /* per slice: the header, then the whole RBSP */
     uint8_t *buf;
     size_t cap;
@@ -146,51 +154,84 @@ typedef struct dcavlc {
 
 static void dcavlc_free(dcavlc_t *dc) {
     if (dc->hdr) for (int i = 0; i < dc->n; i++) jm_bits_free(&dc->hdr[i]);
-    free(dc->d); free(dc->where); free(dc->hdr); free(dc->buf);
+    free(dc->d); free(dc->where); free(dc->cd); free(dc->cwhere); free(dc->hdr); free(dc->buf);
     memset(dc, 0, sizeof(*dc));
 }
-static int dcavlc_init(dcavlc_t *dc, const jm_seq *s) {
+static int dcavlc_init(dcavlc_t *dc, const jm_seq *s, int cabac) {
     const int nmb = s->mbw * s->mbh, step = s->slice_mbs > 0 ? s->slice_mbs : nmb;
     memset(dc, 0, sizeof(*dc));
     dc->n = (nmb + step - 1) / step;
+    dc->cabac = cabac;
     dc->d = (jmh_slice_desc *)calloc(dc->n, sizeof(*dc->d));
     dc->where = (jmh_slice_bytes *)calloc(dc->n, sizeof(*dc->where));
+    dc->cd = (jmh_cabac_slice_desc *)calloc(dc->n, sizeof(*dc->cd));
+    dc->cwhere = (jmh_cabac_slice_bytes *)calloc(dc->n, sizeof(*dc->cwhere));
     dc->hdr = (jm_bits *)calloc(dc->n, sizeof(*dc->hdr));
     dc->cap = (size_t)nmb * 64 + 1024;
     dc->buf = (uint8_t *)malloc(dc->cap);
-    if (!dc->d || !dc->where || !dc->hdr || !dc->buf) { dcavlc_free(dc); return JMH_E_OOM; }
+    if (!dc->d || !dc->where || !dc->cd || !dc->cwhere || !dc->hdr || !dc->buf) { dcavlc_free(dc); return JMH_E_OOM; }
     return JMH_OK;
+}
+static int device_call(dcavlc_t *dc, jm_backend *be) {
+    return dc->cabac ? device_cabac_fn(be->ctx, dc->n, dc->cd, dc->buf, dc->cap, dc->cwhere)
+                     : device_cavlc_fn(be->ctx, dc->n, dc->d, dc->buf, dc->cap, dc->where);
 }
 static int device_picture_slices(dcavlc_t *dc, jm_backend *be, const jm_seq *s, const jm_slice *sl0, jm_bits *out) {
     const int nmb = s->mbw * s->mbh, step = s->slice_mbs > 0 ? s->slice_mbs : nmb;
+    const long len0 = out->len;
     for (int i = 0; i < dc->n; i++) {
         jm_slice sl = *sl0;
         sl.first_mb = i * step;
         jm_bits *h = &dc->hdr[i];
         h->len = 0; h->acc = 0; h->nacc = 0;
         jm_write_slice_header(h, s, &sl);
+        const int n_mb = sl.first_mb + step < nmb ? step : nmb - sl.first_mb;
+        if (dc->cabac) {
+            while (h->nacc) jm_put(h, 1, 1);    /* cabac_alignment_one_bit */
+            dc->cd[i].first_mb = sl.first_mb;
+            dc->cd[i].n_mb = n_mb;
+            dc->cd[i].slice_type = sl0->slice_type;
+            dc->cd[i].slice_qp = sl0->qp;
+            continue;
+        }
         dc->d[i].first_mb = sl.first_mb;
-        dc->d[i].n_mb = sl.first_mb + step < nmb ? step : nmb - sl.first_mb;
+        dc->d[i].n_mb = n_mb;
         dc->d[i].slice_type = sl0->slice_type;
         dc->d[i].lead_nbits = h->nacc;
         dc->d[i].lead_bits = (uint32_t)h->acc;
     }
     memset(dc->where, 0, dc->n * sizeof(*dc->where));
-    int r = device_cavlc_fn(be->ctx, dc->n, dc->d, dc->buf, dc->cap, dc->where);
-    const size_t total = (size_t)(dc->where[dc->n - 1].offset + dc->where[dc->n - 1].nbytes);
+    memset(dc->cwhere, 0, dc->n * sizeof(*dc->cwhere));
+    int r = device_call(dc, be);
+    const size_t total = dc->cabac ? (size_t)(dc->cwhere[dc->n - 1].offset + dc->cwhere[dc->n - 1].nbytes)
+                                   : (size_t)(dc->where[dc->n - 1].offset + dc->where[dc->n - 1].nbytes);
     if (r == JMH_E_INVALID_ARG && total > dc->cap) {   /* the counted size: grow and write again */
         uint8_t *nb = (uint8_t *)realloc(dc->buf, 2 * total);
         if (!nb) return JMH_E_OOM;
         dc->buf = nb; dc->cap = 2 * total;
-        r = device_cavlc_fn(be->ctx, dc->n, dc->d, dc->buf, dc->cap, dc->where);
+        r = device_call(dc, be);
     }
     if (r) return r;
+    long bins = 0;
     for (int i = 0; i < dc->n; i++) {
         jm_bits *h = &dc->hdr[i];
-        jm_bits t = {dc->buf + dc->where[i].offset, dc->where[i].nbytes, dc->where[i].nbytes, 0, 0};
-        h->acc = 0; h->nacc = 0;                /* the partial byte comes back as the first device byte */
+        const int64_t off = dc->cabac ? dc->cwhere[i].offset : dc->where[i].offset;
+        const int64_t nby = dc->cabac ? dc->cwhere[i].nbytes : dc->where[i].nbytes;
+        jm_bits t = {dc->buf + off, nby, nby, 0, 0};
+        h->acc = 0; h->nacc = 0;                /* CAVLC: the partial byte comes back as the first device byte */
         jm_bits_append(h, &t);
         jm_write_nal(out, sl0->idr ? 3 : 2, sl0->idr ? 5 : 1, h);
+        if (dc->cabac) bins += (long)dc->cwhere[i].nbins;
+    }
+    if (dc->cabac) {                            /* cabac_zero_words: as encode_picture_slices */
+        const long bytes = out->len - len0 - 4L * dc->n;
+        const int bd = s->bit_depth > 8 ? s->bit_depth : 8;
+        const long excess = 3 * bins - 36L * bd * nmb - 32 * bytes;
+        for (long z = excess > 0 ? (excess + 95) / 96 : 0; z > 0; z--) {
+            static const uint8_t zw[3] = {0, 0, 3};
+            jm_bits t = {(uint8_t *)zw, 3, 3, 0, 0};
+            jm_bits_append(out, &t);
+        }
     }
     return JMH_OK;
 }
@@ -297,6 +338,11 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fprintf(stderr, "DeviceCAVLC=1 needs the device backend (backend '%s' writes its slices on the host: DeviceCAVLC=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
     }
+    if (inp->device_cabac && !device_cabac_fn) {
+        fprintf(stderr, "DeviceCABAC=1 needs the device backend (backend '%s' writes its slices on the host: DeviceCABAC=0)\n", be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
+    const int device_writer = inp->device_cavlc || inp->device_cabac;
     jmh_config cfg;
     jm_fill_config(inp, &cfg);
     int W = cfg.width, H = cfg.height;
@@ -334,7 +380,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     const int depth = pipelined ? be->depth : 1;
     /* parallel slice writing: pipelined device backend, not with the call surface's per-MB
        device searches (those share the context with the frame loop) */
-    const int nwr = (pipelined && !inp->jm_call_surface && !inp->device_cavlc) ? inp->writer_threads : 0;
+    const int nwr = (pipelined && !inp->jm_call_surface && !device_writer) ? inp->writer_threads : 0;
     const int nj = nwr ? 2 * nwr : 0;                  /* jobs in flight: queued + running + done */
     const int plen = depth + nj + 1;                   /* source slots: a job's source stays put */
     typedef struct { jm_pic cur; jmh_frame_params fp; int f, is_i, frame_num; } pend_t;
@@ -367,7 +413,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     jm_bits out, rbsp;
     jm_bits_init(&out); jm_bits_init(&rbsp);
     if (!res || jm86_init(&im, inp, be, W, H)) { st_ret = JMH_E_OOM; goto cleanup; }
-    if (inp->device_cavlc && dcavlc_init(&dc, &s)) { st_ret = JMH_E_OOM; goto cleanup; }
+    if (device_writer && dcavlc_init(&dc, &s, inp->device_cabac)) { st_ret = JMH_E_OOM; goto cleanup; }
     if (nwr) {
         pool.nj = nj; pool.s = &s; pool.inp = inp; pool.nth = nwr;
         pool.jobs = (wjob_t *)calloc(nj, sizeof(wjob_t));
@@ -399,6 +445,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         if (pipelined) fprintf(log, " (%d pictures in flight%s)\n", depth, nwr ? ", parallel slice writing" : "");
         if (nwr) fprintf(log, " (%d slice-writer threads)\n", nwr);
         if (inp->device_cavlc) fprintf(log, " (CAVLC slice data written on the device)\n");
+        if (inp->device_cabac) fprintf(log, " (CABAC slice data written on the device: no writer threads, no per-macroblock rate check)\n");
         fprintf(log, " Frame  Bit/pic  QP   SnrY    SnrU    SnrV    Time(ms) MET(ms) Frm/Fld  I D\n");
     }
     double t_start = now_ms();
@@ -459,9 +506,9 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         sl.idr = p_->f == 0; sl.slice_type = p_->fp.slice_type; sl.frame_num = p_->frame_num;      \
         sl.poc_lsb = 2 * p_->f; sl.idr_pic_id = 0; sl.qp = p_->fp.qp;                              \
         sl.first_mb = 0;                                                                           \
-        { int e_ = inp->device_cavlc ? device_picture_slices(&dc, be, &s, &sl, &out)                \
+        { int e_ = device_writer ? device_picture_slices(&dc, be, &s, &sl, &out)                \
                                      : encode_picture_slices(&im, &s, &sl, &p_->fp, &p_->cur, &rec, &out); \
-          if (e_) { if (inp->device_cavlc) fprintf(stderr, "device CAVLC writer failed: status %d\n", e_); st_ret = e_; break; } } \
+          if (e_) { if (device_writer) fprintf(stderr, "device slice writer failed: status %d\n", e_); st_ret = e_; break; } } \
         double t2 = now_ms();                                                                      \
         st->entropy_ms += t2 - t1;                                                                 \
         long pic_bits = out.len * 8;                                                               \
@@ -590,7 +637,7 @@ cleanup:
                 st->total_ms / 1e3, st->me_tq_ms / 1e3, st->psnr_y, st->psnr_u, st->psnr_v, st->bits);
     if (log && st->frames)
         fprintf(log, " Host per picture: slice writing + PSNR %.2f ms (%s), results + readback (+ host deblocking) %.2f ms, wall %.2f ms\n",
-                st->entropy_ms / st->frames, nwr ? "writer threads" : inp->device_cavlc ? "the device call, no PSNR" : "main thread", st->deblock_ms / st->frames,
+                st->entropy_ms / st->frames, nwr ? "writer threads" : device_writer ? "the device call, no PSNR" : "main thread", st->deblock_ms / st->frames,
                 st->total_ms / st->frames);
     if (log && st->frames)
         fprintf(log, " Main thread per picture: read %.2f ms, push %.2f, pop (wait) %.2f, results to writer %.2f, flush %.2f\n",

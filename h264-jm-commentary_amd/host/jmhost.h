@@ -75,6 +75,8 @@ typedef struct jm_input {
     int  device_cavlc;         /* (this build) DeviceCAVLC 1: the CAVLC slice data is written on the
                                   device (jmh_cavlc_write_slices); the host keeps the slice headers
                                   and the NAL packaging.  SymbolMode 0, device backend only        */
+    int  device_cabac;         /* (this build) DeviceCABAC 1: the same for CABAC slice data (jmh_cabac
+                                  _write_slices).  SymbolMode 1, device backend only               */
     int  verbose;
 } jm_input;
 
@@ -175,6 +177,17 @@ void jm_write_slice_header(jm_bits *rbsp, const jm_seq *s, const jm_slice *sl);
    header's whole bytes.  where[n] is filled whenever the descriptors are valid */
 int  jm_cavlc_ref(int width, int height, int transform_8x8_mode, int constrained_intra, const jmh_mb_result *res, int n,
                   const jmh_slice_desc *slices, uint8_t *out, size_t cap, jmh_slice_bytes *where);
+/* CABAC bins of the slices closed so far; the longest run of outstanding bits the coder resolved */
+long jm_slice_bins(const jm_slice_writer *w);
+int  jm_slice_max_outstanding(const jm_slice_writer *w);
+/* host/cabac_ref.c: the CABAC writer (cabac.c) behind the calling convention of jmh_cabac_write
+   _results, flat arguments: per slice the bytes behind the slice header and its cabac_alignment_one
+   _bits, and the slice's bins.  where[n] is filled whenever the descriptors are valid.  The slice QP
+   is 0..51 at every bit depth (the host takes no QpBdOffset in QPISlice / QPPSlice), so no bit depth
+   is passed.  jm_cabac_ref_max_outstanding: the longest run of outstanding bits of the last call */
+int  jm_cabac_ref(int width, int height, int transform_8x8_mode, int constrained_intra, const jmh_mb_result *res, int n,
+                  const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap, jmh_cabac_slice_bytes *where);
+int  jm_cabac_ref_max_outstanding(void);
 
 /* ---- deblocking (H.264 8.7), in place on the reconstructed picture ---------------------- */
 void jm_deblock_picture(jm_pic *p, const jm_seq *s, const jmh_mb_result *const *res, int qp);
@@ -216,6 +229,10 @@ typedef struct jm_backend {
    positional initialisers stay as they are. */
 typedef int (*jm_cavlc_slices_fn)(void *ctx, int n, const jmh_slice_desc *slices, uint8_t *out, size_t cap, jmh_slice_bytes *where);
 void jm_set_device_cavlc(jm_cavlc_slices_fn fn);
+/* DeviceCABAC 1: the same for the CABAC slice data (jmh_cabac_write_slices) */
+typedef int (*jm_cabac_slices_fn)(void *ctx, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap,
+                                  jmh_cabac_slice_bytes *where);
+void jm_set_device_cabac(jm_cabac_slices_fn fn);
 
 typedef struct jm_stats {
     int frames;

@@ -46,6 +46,9 @@ static int gpu_tq4x4(void *ctx, int n, const int16_t *resid, const uint8_t *pred
 static int gpu_cavlc_slices(void *ctx, int n, const jmh_slice_desc *d, uint8_t *out, size_t cap, jmh_slice_bytes *where) {
     return jmh_cavlc_write_slices((jmh_ctx *)ctx, n, d, out, cap, where);
 }
+static int gpu_cabac_slices(void *ctx, int n, const jmh_cabac_slice_desc *d, uint8_t *out, size_t cap, jmh_cabac_slice_bytes *where) {
+    return jmh_cabac_write_slices((jmh_ctx *)ctx, n, d, out, cap, where);
+}
 
 int main(int argc, char **argv) {
     jm_input inp;
@@ -64,6 +67,7 @@ int main(int argc, char **argv) {
                      gpu_deblocked, gpu_ref_deblocked, gpu_push, gpu_pop, jmh_pipeline_depth(ctx),
                      gpu_search_pictures, gpu_block_search, gpu_tq4x4};
     jm_set_device_cavlc(gpu_cavlc_slices);
+    jm_set_device_cabac(gpu_cabac_slices);
     if (getenv("JMH_HOST_DEBLOCK")) be.read_deblocked = NULL, be.reference_deblocked = NULL;
     jm_stats st;
     r = jm_encode_sequence(&inp, &be, &st, stdout);

@@ -169,6 +169,40 @@ def slice_descs(nmb, slice_type, mbs_per_slice=0, lead=()):
     return d
 
 
+# ---- CABAC slice data on the device (include/jmhip_cabac.h; additive to ABI 14) ----
+class JmhCabacSliceDesc(ctypes.Structure):
+    _fields_ = [("first_mb", ctypes.c_int32), ("n_mb", ctypes.c_int32), ("slice_type", ctypes.c_int32), ("slice_qp", ctypes.c_int32)]
+
+
+class JmhCabacSliceBytes(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("nbytes", ctypes.c_int64), ("nbins", ctypes.c_int64)]
+
+
+JMC_MB_MAX_BINS = 18944          # csrc/jmh_cabac_write.h: the worst case of one macroblock, in bins
+_SIGS_CABAC = {
+    "jmh_cabac_write_slices": (_I, [_P, _I, _P, _P, ctypes.c_size_t, _P]),
+    "jmh_cabac_write_results": (_I, [_P, _P, _I, _P, _P, ctypes.c_size_t, _P]),
+}
+EXPORTED_CABAC = tuple(_SIGS_CABAC)
+
+
+def cabac_max_bytes(nmb, nslices):
+    """csrc/jmh_cabac_write.h: JMC_SLICE_MAX_BYTES of every slice at JMC_MB_MAX_BINS per macroblock."""
+    return (7 * nmb * JMC_MB_MAX_BINS + 9 * nslices) // 8 + nslices
+
+
+def cabac_slice_descs(nmb, slice_type, qp, mbs_per_slice=0):
+    """Raster runs of mbs_per_slice macroblocks (0: one slice) covering nmb macroblocks, as a
+    JmhCabacSliceDesc array; qp: the slice QP, or a sequence of them, cycled."""
+    step = mbs_per_slice if mbs_per_slice > 0 else nmb
+    firsts = list(range(0, nmb, step))
+    qps = [qp] if isinstance(qp, int) else list(qp)
+    d = (JmhCabacSliceDesc * len(firsts))()
+    for i, f in enumerate(firsts):
+        d[i] = JmhCabacSliceDesc(f, min(step, nmb - f), slice_type, qps[i % len(qps)])
+    return d
+
+
 class JmhError(RuntimeError):
     status = None                # the JMH_E_* code, where a jmh_* call failed
 
@@ -184,7 +218,7 @@ def load(path=LIB_PATH):
     if not os.path.exists(path):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -411,6 +445,32 @@ class Encoder:
         return self._cavlc(lambda *a: self.lib.jmh_cavlc_write_results(self.ctx, _ptr(res), *a), "jmh_cavlc_write_results", descs, cap,
                            with_where)
 
+    # ---- CABAC slice data on the device (jmh_cabac_write_slices / _results) ----
+    def _cabac(self, call, what, descs, cap, with_where):
+        n = len(descs)
+        if cap is None:          # the documented bound: no picture needs more
+            cap = cabac_max_bytes(self.mbw * self.mbh, n)
+        out = np.zeros(max(cap, 1), np.uint8)
+        where = (JmhCabacSliceBytes * n)()
+        _check(call(n, ctypes.cast(descs, _P), _ptr(out), cap, ctypes.cast(where, _P)), what)
+        data = [out[w.offset:w.offset + w.nbytes].tobytes() for w in where]
+        return (data, [(w.offset, w.nbytes, w.nbins) for w in where]) if with_where else data
+
+    def cabac_slices(self, descs, cap=None, with_where=False):
+        """The CABAC slice_data() up to the rbsp_stop_one_bit of every slice (a JmhCabacSliceDesc array,
+        see cabac_slice_descs) of the picture last popped / waited for, written on the device: a list of
+        bytes, one per slice (behind each slice header and its cabac_alignment_one_bits they are the
+        slice's RBSP).  with_where: also (offset, nbytes, nbins) per slice."""
+        return self._cabac(lambda *a: self.lib.jmh_cabac_write_slices(self.ctx, *a), "jmh_cabac_write_slices", descs, cap, with_where)
+
+    def cabac_results(self, res, descs, cap=None, with_where=False):
+        """The same for caller-supplied results (MB_RESULT_DTYPE[mbw * mbh]); no picture needed."""
+        res = np.ascontiguousarray(res, MB_RESULT_DTYPE)
+        if res.size != self.mbw * self.mbh:
+            raise JmhError(f"cabac_results: {res.size} results for {self.mbw * self.mbh} macroblocks")
+        return self._cabac(lambda *a: self.lib.jmh_cabac_write_results(self.ctx, _ptr(res), *a), "jmh_cabac_write_results", descs, cap,
+                           with_where)
+
     # ---- unit seams ----
     def sad_table(self, mb_xy, centres):
         mb_xy = np.ascontiguousarray(mb_xy, np.int32)
@@ -528,6 +588,25 @@ def cavlc_ref(width, height, transform_8x8_mode, constrained_intra, res, descs, 
                              ctypes.cast(where, _P)), "jm_cavlc_ref")
     data = [out[w.offset:w.offset + w.nbytes].tobytes() for w in where]
     return (data, [(w.offset, w.nbytes, w.nbits) for w in where]) if with_where else data
+
+
+def cabac_ref(width, height, transform_8x8_mode, constrained_intra, res, descs, with_where=False, cap=None):
+    """The host CABAC writer (host/cabac.c through host/cabac_ref.c) behind the arguments of
+    Encoder.cabac_results: the reference of the device writer.  A list of bytes, one per slice;
+    with_where: also (offset, nbytes, nbins) per slice."""
+    host = load_host()
+    host.jm_cabac_ref.restype = _I
+    host.jm_cabac_ref.argtypes = [_I, _I, _I, _I, _P, _I, _P, _P, ctypes.c_size_t, _P]
+    res = np.ascontiguousarray(res, MB_RESULT_DTYPE)
+    n = len(descs)
+    if cap is None:
+        cap = cabac_max_bytes(res.size, n)
+    out = np.zeros(max(cap, 1), np.uint8)
+    where = (JmhCabacSliceBytes * n)()
+    _check(host.jm_cabac_ref(width, height, transform_8x8_mode, constrained_intra, _ptr(res), n, ctypes.cast(descs, _P), _ptr(out), cap,
+                             ctypes.cast(where, _P)), "jm_cabac_ref")
+    data = [out[w.offset:w.offset + w.nbytes].tobytes() for w in where]
+    return (data, [(w.offset, w.nbytes, w.nbins) for w in where]) if with_where else data
 
 
 def deblock_ref(rec_yuv, results, mbw, mbh, qp, chroma_qp_offset=0, alpha_div2=0, beta_div2=0, bit_depth=8):
