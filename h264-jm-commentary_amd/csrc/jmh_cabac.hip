@@ -18,9 +18,14 @@
 //   k_cabac_where   one workgroup: scan of the slices' byte counts: where[], the total.
 //   k_cabac_pack    copies every slice from the scratch buffer to its place in the output.
 //
-// The host learns the bins between scan and bins (it sizes the record and scratch buffers from them)
-// and the bytes between where and pack (the capacity check), each by a copy on the writer's stream,
-// which only that stream is waited for.  No workgroup waits on another, every loop is bounded by a
+// Two callers queue these launches.  The synchronous entry points (jmh_cabac_run) learn the bins
+// between scan and bins (they size the record and scratch buffers from them) and the bytes between
+// where and pack (the capacity check), each by a copy on the writer's stream, which only that stream
+// is waited for.  A coded picture (jmh_cabac_enqueue) queues all six behind the
+// picture's last macroblock with no host wait: the buffers have capacities decided before, k_cabac_scan
+// (bins, scratch) and k_cabac_where (output bytes) set the picture's overflow word when a counted
+// size exceeds its capacity, and every later launch of that picture returns at once when it is set
+// -- a device-side predicate, no store out of bounds; the host sees the word at the pop.  No workgroup waits on another, every loop is bounded by a
 // counted size, and the coder cannot overflow its scratch: it is sized from the bound of its bins.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -154,8 +159,11 @@ __device__ uint64_t cb_block_scan(uint64_t v, uint64_t *buf, uint64_t *total) {
     return incl - v;
 }
 
-// totals[0]: the picture's bins, totals[1]: the scratch bytes that hold every slice's bound
-__global__ __launch_bounds__(1024) void k_cabac_scan(CbPic p, const uint32_t *mb_bins, uint64_t *mb_off, uint64_t *sl_soff, uint64_t *totals) {
+// totals[0]: the picture's bins, totals[1]: the scratch bytes that hold every slice's bound.
+// ovf (may be null): set when either exceeds its capacity, decided before the enqueue; the later
+// passes of that picture then write nothing (coded pictures)
+__global__ __launch_bounds__(1024) void k_cabac_scan(CbPic p, const uint32_t *mb_bins, uint64_t *mb_off, uint64_t *sl_soff, uint64_t *totals,
+                                                     uint64_t rec_cap, uint64_t scratch_cap, uint32_t *ovf) {
     __shared__ uint64_t buf[2048];
     const int t = threadIdx.x;
     uint64_t total;
@@ -165,7 +173,10 @@ __global__ __launch_bounds__(1024) void k_cabac_scan(CbPic p, const uint32_t *mb
         for (int a = b0; a < b1; a++) s += mb_bins[a];
         uint64_t e = cb_block_scan(s, buf, &total);
         for (int a = b0; a < b1; a++) { mb_off[a] = e; e += mb_bins[a]; }
-        if (t == 0) { mb_off[p.nmb] = total; totals[0] = total; }
+        if (t == 0) {
+            mb_off[p.nmb] = total; totals[0] = total;
+            if (ovf && total > rec_cap) *ovf = 1u;
+        }
     }
     __syncthreads();
     {   // slices: the bound of their bytes (whole dwords: the coder stores dwords), scratch offsets
@@ -181,14 +192,17 @@ __global__ __launch_bounds__(1024) void k_cabac_scan(CbPic p, const uint32_t *mb
             sl_soff[i] = e;
             e += cb_align4(JMC_SLICE_MAX_BYTES(mb_off[d.first_mb + d.n_mb] - mb_off[d.first_mb]));
         }
-        if (t == 0) { sl_soff[p.nslices] = total; totals[1] = total; }
+        if (t == 0) {
+            sl_soff[p.nslices] = total; totals[1] = total;
+            if (ovf && total > scratch_cap) *ovf = 1u;
+        }
     }
 }
 
 __global__ __launch_bounds__(64 * CB_WAVES) void k_cabac_bins(CbPic p, const uint16_t *unit_bins, const int32_t *mb_slice,
-                                                              const uint64_t *mb_off, uint16_t *rec, uint64_t rec_cap) {
+                                                              const uint64_t *mb_off, uint16_t *rec, uint64_t rec_cap, const uint32_t *ovf) {
     const int lane = threadIdx.x & 63, a = blockIdx.x * CB_WAVES + (threadIdx.x >> 6);
-    if (a >= p.nmb) return;                                      // whole wave
+    if (a >= p.nmb || (ovf && *ovf)) return;                     // whole wave; whole grid: a count exceeds its capacity
     const jmw_slice sl = cb_slice(p.sl[mb_slice[a]]);
     const jmw_pic pic = cb_pic(p);
     const uint32_t ub = lane < 32 ? unit_bins[(size_t)a * 32 + lane] : 0u;
@@ -205,9 +219,10 @@ __global__ __launch_bounds__(64 * CB_WAVES) void k_cabac_bins(CbPic p, const uin
 }
 
 __global__ __launch_bounds__(64) void k_cabac_code(CbPic p, const uint64_t *mb_off, const uint64_t *sl_soff, const uint16_t *rec,
-                                                   uint8_t *scratch, int64_t *sl_bytes) {
+                                                   uint8_t *scratch, int64_t *sl_bytes, const uint32_t *ovf) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[CB_STAGE];
     const int lane = threadIdx.x, si = blockIdx.x;
+    if (ovf && *ovf) return;                                     // whole grid
     const jmh_cabac_slice_desc d = p.sl[si];
     jmc_enc e;
     for (int k = 0; k < 5; k++) e.cv[k] = 64 * k + lane < JMR_NCTX ? jmr_init_one(64 * k + lane, d.slice_type == JMH_I_SLICE, d.slice_qp) : 0u;
@@ -234,9 +249,10 @@ __global__ __launch_bounds__(64) void k_cabac_code(CbPic p, const uint64_t *mb_o
 }
 
 __global__ __launch_bounds__(1024) void k_cabac_where(CbPic p, const uint64_t *mb_off, const int64_t *sl_bytes, jmh_cabac_slice_bytes *where,
-                                                      int64_t *total_bytes) {
+                                                      int64_t *total_bytes, uint64_t out_cap, uint32_t *ovf) {
     __shared__ uint64_t buf[2048];
     const int t = threadIdx.x;
+    if (ovf && *ovf) return;                                     // every thread, before the first barrier (written below, behind the last)
     const int per = (p.nslices + 1023) / 1024, b0 = min(t * per, p.nslices), b1 = min(b0 + per, p.nslices);
     uint64_t s = 0, total;
     int bad = 0;
@@ -250,11 +266,15 @@ __global__ __launch_bounds__(1024) void k_cabac_where(CbPic p, const uint64_t *m
         e += (uint64_t)(sl_bytes[i] < 0 ? 0 : sl_bytes[i]);
     }
     const int anybad = __syncthreads_or(bad);
-    if (t == 0) *total_bytes = anybad ? -1 : (int64_t)total;
+    if (t == 0) {
+        *total_bytes = anybad ? -1 : (int64_t)total;
+        if (ovf && total > out_cap) *ovf = 1u;                   // the picture's output region is too small: pack writes nothing
+    }
 }
 
 __global__ __launch_bounds__(256) void k_cabac_pack(const jmh_cabac_slice_bytes *where, const uint64_t *sl_soff, const uint8_t *scratch,
-                                                    uint8_t *out, uint64_t out_cap) {
+                                                    uint8_t *out, uint64_t out_cap, const uint32_t *ovf) {
+    if (ovf && *ovf) return;                                     // whole grid
     const jmh_cabac_slice_bytes w = where[blockIdx.x];
     const uint8_t *src = scratch + sl_soff[blockIdx.x];
     for (int64_t k = (int64_t)blockIdx.y * 256 + threadIdx.x; k < w.nbytes; k += 256 * CB_PACK_Y)
@@ -333,11 +353,10 @@ static int cb_grow(jmh_cabac_state *s, void **buf, size_t *cap_bytes, size_t nee
     return JMH_OK;
 }
 
-int jmh_cabac_run(jmh_cabac_state **state, const jmh_mb_result *d_res, const jmh_mb_result *h_res, hipEvent_t after, int mbw, int mbh,
-                  int t8mode, int cip, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap, jmh_cabac_slice_bytes *where) {
-    const int nmb = mbw * mbh;
-    if (n <= 0 || n > nmb || !slices || !where || (!d_res && !h_res)) return JMH_E_INVALID_ARG;
-    int next = 0;                            // raster runs covering the picture
+// raster runs covering the picture
+int jmh_cabac_check(int nmb, int n, const jmh_cabac_slice_desc *slices) {
+    if (n <= 0 || n > nmb || !slices) return JMH_E_INVALID_ARG;
+    int next = 0;
     for (int i = 0; i < n; i++) {
         const jmh_cabac_slice_desc &d = slices[i];
         if (d.first_mb != next || d.n_mb <= 0 || d.n_mb > nmb - next) return JMH_E_INVALID_ARG;
@@ -345,11 +364,75 @@ int jmh_cabac_run(jmh_cabac_state **state, const jmh_mb_result *d_res, const jmh
         if (d.slice_qp < 0 || d.slice_qp > 51) return JMH_E_INVALID_ARG;
         next += d.n_mb;
     }
-    if (next != nmb) return JMH_E_INVALID_ARG;
+    return next == nmb ? JMH_OK : JMH_E_INVALID_ARG;
+}
+
+// the enqueue half in three parts; between them the synchronous call reads the counts back and sizes
+// its buffers, the coded pictures' enqueue queues them back to back against capacities decided before
+static int cb_enqueue_count(jmh_cabac_state *s, const CbPic &p, uint64_t *d_totals, uint64_t rec_cap, uint64_t scratch_cap, uint32_t *d_ovf) {
+    const int grid = (p.nmb + CB_WAVES - 1) / CB_WAVES;
+    hipLaunchKernelGGL(k_cabac_count, dim3(grid), dim3(64 * CB_WAVES), 0, s->st, p, s->d_unit, s->d_bins, s->d_slice);
+    CBCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cabac_scan, dim3(1), dim3(1024), 0, s->st, p, s->d_bins, s->d_off, s->d_soff, d_totals, rec_cap, scratch_cap, d_ovf);
+    CBCHK(hipGetLastError());
+    return JMH_OK;
+}
+static int cb_enqueue_code(jmh_cabac_state *s, const CbPic &p, jmh_cabac_slice_bytes *d_where, int64_t *d_total, uint64_t out_cap,
+                           uint32_t *d_ovf) {
+    const int grid = (p.nmb + CB_WAVES - 1) / CB_WAVES;
+    hipLaunchKernelGGL(k_cabac_bins, dim3(grid), dim3(64 * CB_WAVES), 0, s->st, p, s->d_unit, s->d_slice, s->d_off, s->d_rec,
+                       (uint64_t)(s->rec_cap / sizeof(uint16_t)), d_ovf);
+    CBCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cabac_code, dim3(p.nslices), dim3(64), 0, s->st, p, s->d_off, s->d_soff, s->d_rec, s->d_scratch, s->d_slbytes, d_ovf);
+    CBCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cabac_where, dim3(1), dim3(1024), 0, s->st, p, s->d_off, s->d_slbytes, d_where, d_total, out_cap, d_ovf);
+    CBCHK(hipGetLastError());
+    return JMH_OK;
+}
+static int cb_enqueue_pack(jmh_cabac_state *s, int n, const jmh_cabac_slice_bytes *d_where, uint8_t *d_out, uint64_t out_cap, const uint32_t *d_ovf) {
+    hipLaunchKernelGGL(k_cabac_pack, dim3(n, CB_PACK_Y), dim3(256), 0, s->st, d_where, s->d_soff, s->d_scratch, d_out, out_cap, d_ovf);
+    CBCHK(hipGetLastError());
+    return JMH_OK;
+}
+
+// Capacities of the coder's shared buffers for a picture of out_cap output bytes: JMH_CODED_BINS_PER_BYTE
+// bins per output byte (a bypass bin costs one bit and a context-coded bin less, so a picture holds
+// somewhat more than 8 bins per byte; 10 is a margin, not a measurement), and the scratch that
+// holds every slice's bound for that many bins
+#define JMH_CODED_BINS_PER_BYTE 10
+int jmh_cabac_enqueue(jmh_cabac_state **state, const jmh_mb_result *d_res, hipEvent_t after, int mbw, int mbh, int t8mode, int cip, int n,
+                      const jmh_writer_job *job, hipStream_t *stream) {
+    const int nmb = mbw * mbh;
     if (!*state) *state = new jmh_cabac_state();
     jmh_cabac_state *s = *state;
     int r = cb_setup(s, nmb);
     if (r) return r;
+    *stream = s->st;
+    const size_t rec_need = job->out_cap * JMH_CODED_BINS_PER_BYTE * sizeof(uint16_t);
+    const size_t scr_need = (size_t)JMC_SLICE_MAX_BYTES(job->out_cap * JMH_CODED_BINS_PER_BYTE) + 4 * (size_t)nmb;
+    if ((r = cb_grow(s, (void **)&s->d_rec, &s->rec_cap, rec_need, 0))) return r;
+    if ((r = cb_grow(s, (void **)&s->d_scratch, &s->scratch_cap, scr_need, 0))) return r;
+    CBCHK(hipStreamWaitEvent(s->st, after, 0));
+    CBCHK(hipMemcpyAsync(job->d_sl, job->h_sl, (size_t)n * sizeof(jmh_cabac_slice_desc), hipMemcpyHostToDevice, s->st));
+    CBCHK(hipMemsetAsync(job->d_meta, 0, JMH_WRITER_META_BYTES, s->st));
+    CbPic p;
+    p.res = d_res; p.mbw = mbw; p.mbh = mbh; p.t8mode = t8mode; p.cip = cip; p.nmb = nmb; p.nslices = n;
+    p.sl = (const jmh_cabac_slice_desc *)job->d_sl;
+    uint32_t *ovf = (uint32_t *)(job->d_meta + 1);
+    if ((r = cb_enqueue_count(s, p, job->d_meta + 5, (uint64_t)(s->rec_cap / sizeof(uint16_t)), (uint64_t)s->scratch_cap, ovf))) return r;
+    if ((r = cb_enqueue_code(s, p, (jmh_cabac_slice_bytes *)job->d_where, (int64_t *)job->d_meta, (uint64_t)job->out_cap, ovf))) return r;
+    return cb_enqueue_pack(s, n, (const jmh_cabac_slice_bytes *)job->d_where, job->d_out, (uint64_t)job->out_cap, ovf);
+}
+
+int jmh_cabac_run(jmh_cabac_state **state, const jmh_mb_result *d_res, const jmh_mb_result *h_res, hipEvent_t after, int mbw, int mbh,
+                  int t8mode, int cip, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap, jmh_cabac_slice_bytes *where) {
+    const int nmb = mbw * mbh;
+    if (!where || (!d_res && !h_res)) return JMH_E_INVALID_ARG;
+    int r = jmh_cabac_check(nmb, n, slices);
+    if (r) return r;
+    if (!*state) *state = new jmh_cabac_state();
+    jmh_cabac_state *s = *state;
+    if ((r = cb_setup(s, nmb))) return r;
     if (h_res) {
         if (!s->d_res && hipMalloc((void **)&s->d_res, (size_t)nmb * sizeof(jmh_mb_result)) != hipSuccess) return JMH_E_OOM;
         CBCHK(hipMemcpyAsync(s->d_res, h_res, (size_t)nmb * sizeof(jmh_mb_result), hipMemcpyHostToDevice, s->st));
@@ -358,25 +441,15 @@ int jmh_cabac_run(jmh_cabac_state **state, const jmh_mb_result *d_res, const jmh
     CBCHK(hipMemcpyAsync(s->d_sl, slices, (size_t)n * sizeof(jmh_cabac_slice_desc), hipMemcpyHostToDevice, s->st));
     CbPic p;
     p.res = d_res; p.mbw = mbw; p.mbh = mbh; p.t8mode = t8mode; p.cip = cip; p.nmb = nmb; p.nslices = n; p.sl = s->d_sl;
-    const int grid = (nmb + CB_WAVES - 1) / CB_WAVES;
     uint64_t *h_totals = (uint64_t *)(s->h_where + nmb + 1);     // two counts behind where[] and the total
-    hipLaunchKernelGGL(k_cabac_count, dim3(grid), dim3(64 * CB_WAVES), 0, s->st, p, s->d_unit, s->d_bins, s->d_slice);
-    CBCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_cabac_scan, dim3(1), dim3(1024), 0, s->st, p, s->d_bins, s->d_off, s->d_soff, s->d_totals);
-    CBCHK(hipGetLastError());
+    if ((r = cb_enqueue_count(s, p, s->d_totals, 0, 0, nullptr))) return r;
     CBCHK(hipMemcpyAsync(h_totals, s->d_totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s->st));
     CBCHK(hipStreamSynchronize(s->st));      // the writer's own stream only
     const uint64_t nbins = h_totals[0], nscratch = h_totals[1];
     if (nbins == 0 || nbins > (uint64_t)nmb * JMC_MB_MAX_BINS) return JMH_E_STATE;   // the documented bound
     if ((r = cb_grow(s, (void **)&s->d_rec, &s->rec_cap, (size_t)nbins * sizeof(uint16_t), (size_t)nmb * 256))) return r;
     if ((r = cb_grow(s, (void **)&s->d_scratch, &s->scratch_cap, (size_t)nscratch, (size_t)nmb * 128))) return r;
-    hipLaunchKernelGGL(k_cabac_bins, dim3(grid), dim3(64 * CB_WAVES), 0, s->st, p, s->d_unit, s->d_slice, s->d_off, s->d_rec,
-                       (uint64_t)(s->rec_cap / sizeof(uint16_t)));
-    CBCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_cabac_code, dim3(n), dim3(64), 0, s->st, p, s->d_off, s->d_soff, s->d_rec, s->d_scratch, s->d_slbytes);
-    CBCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_cabac_where, dim3(1), dim3(1024), 0, s->st, p, s->d_off, s->d_slbytes, s->d_where, s->d_total);
-    CBCHK(hipGetLastError());
+    if ((r = cb_enqueue_code(s, p, s->d_where, s->d_total, 0, nullptr))) return r;
     CBCHK(hipMemcpyAsync(s->h_where, s->d_where, (size_t)n * sizeof(jmh_cabac_slice_bytes), hipMemcpyDeviceToHost, s->st));
     CBCHK(hipMemcpyAsync(s->h_where + nmb, s->d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s->st));
     CBCHK(hipStreamSynchronize(s->st));
@@ -385,8 +458,7 @@ int jmh_cabac_run(jmh_cabac_state **state, const jmh_mb_result *d_res, const jmh
     memcpy(where, s->h_where, (size_t)n * sizeof(jmh_cabac_slice_bytes));
     if (!out || (size_t)total > cap) return JMH_E_INVALID_ARG;    // before anything is copied: out untouched
     if ((r = cb_grow(s, (void **)&s->d_out, &s->out_cap, (size_t)total, (size_t)nmb * 64))) return r;
-    hipLaunchKernelGGL(k_cabac_pack, dim3(n, CB_PACK_Y), dim3(256), 0, s->st, s->d_where, s->d_soff, s->d_scratch, s->d_out, (uint64_t)total);
-    CBCHK(hipGetLastError());
+    if ((r = cb_enqueue_pack(s, n, s->d_where, s->d_out, (uint64_t)total, nullptr))) return r;
     CBCHK(hipMemcpyAsync(out, s->d_out, (size_t)total, hipMemcpyDeviceToHost, s->st));
     CBCHK(hipStreamSynchronize(s->st));
     return JMH_OK;

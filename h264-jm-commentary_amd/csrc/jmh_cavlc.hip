@@ -19,9 +19,13 @@
 //                   bits, its last one the rbsp_stop_one_bit (the alignment zeros are the zeroed
 //                   buffer).  Output words are byte-swapped: bits are MSB first within bytes.
 //
-// The host learns the byte count between scan and write (a copy on the writer's stream, which only
-// that stream is waited for), so the capacity check uses the counted bits and the write pass has no
-// overflow path.  One-macroblock-per-lane was not built: it would leave a 1080p picture at 128 waves
+// Two callers queue these passes.  The synchronous entry points (jmh_cavlc_run) read the byte count
+// back between scan and write (a copy on the writer's stream, which only that stream is waited for)
+// and size the output from it.  A coded picture (jmh_cavlc_enqueue) queues all three
+// behind the picture's last macroblock with no host wait: the output region has a capacity decided
+// before, k_cavlc_scan sets the picture's overflow word when the counted bytes exceed it, and
+// k_cavlc_write then writes nothing -- a device-side predicate, no store out of bounds; the host
+// sees the word at the pop.  One-macroblock-per-lane was not built: it would leave a 1080p picture at 128 waves
 // of fully divergent serial work (not measured).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -99,8 +103,10 @@ __device__ uint64_t cv_block_scan(uint64_t v, uint64_t *buf, uint64_t *total) {
     return incl - v;
 }
 
+// ovf (may be null): set when the counted bytes exceed cap_bytes, the capacity decided before the
+// enqueue; the write pass of that picture then writes nothing (coded pictures)
 __global__ __launch_bounds__(1024) void k_cavlc_scan(CvPic p, const uint32_t *mb_bits, uint64_t *mb_off, jmh_slice_bytes *where,
-                                                     int64_t *total_bytes) {
+                                                     int64_t *total_bytes, uint64_t cap_bytes, uint32_t *ovf) {
     __shared__ uint64_t buf[2048];
     const int t = threadIdx.x;
     uint64_t total;
@@ -125,14 +131,19 @@ __global__ __launch_bounds__(1024) void k_cavlc_scan(CvPic p, const uint32_t *mb
         }
         uint64_t e = cv_block_scan(s, buf, &total);
         for (int i = b0; i < b1; i++) { where[i].offset = (int64_t)e; e += (uint64_t)where[i].nbytes; }
-        if (t == 0) *total_bytes = (int64_t)total;
+        if (t == 0) {
+            *total_bytes = (int64_t)total;
+            if (ovf && total > cap_bytes) *ovf = 1u;
+        }
     }
 }
 
 __global__ __launch_bounds__(64 * CV_WAVES) void k_cavlc_write(CvPic p, const uint16_t *unit_bits, const uint32_t *mb_bits,
                                                                const int32_t *mb_run, const int32_t *mb_slice, const uint64_t *mb_off,
-                                                               const jmh_slice_bytes *where, uint32_t *out, uint64_t out_words) {
+                                                               const jmh_slice_bytes *where, uint32_t *out, uint64_t out_words,
+                                                               const uint32_t *ovf) {
     __shared__ uint32_t stage_all[CV_WAVES][CV_STAGE];
+    if (ovf && *ovf) return;                                     // the whole grid: the counted bytes exceed the capacity
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, a = blockIdx.x * CV_WAVES + wave;
     const bool act = a < p.nmb;                                  // wave-uniform; every wave reaches the barriers
     uint32_t *stage = stage_all[wave];
@@ -250,11 +261,10 @@ static int cv_setup(jmh_cavlc_state *s, int nmb, int n) {
     return JMH_OK;
 }
 
-int jmh_cavlc_run(jmh_cavlc_state **state, const jmh_mb_result *d_res, const jmh_mb_result *h_res, hipEvent_t after, int mbw, int mbh,
-                  int t8mode, int cip, int n, const jmh_slice_desc *slices, uint8_t *out, size_t cap, jmh_slice_bytes *where) {
-    const int nmb = mbw * mbh;
-    if (n <= 0 || n > nmb || !slices || !where || (!d_res && !h_res)) return JMH_E_INVALID_ARG;
-    int next = 0;                            // raster runs covering the picture
+// raster runs covering the picture
+int jmh_cavlc_check(int nmb, int n, const jmh_slice_desc *slices) {
+    if (n <= 0 || n > nmb || !slices) return JMH_E_INVALID_ARG;
+    int next = 0;
     for (int i = 0; i < n; i++) {
         const jmh_slice_desc &d = slices[i];
         if (d.first_mb != next || d.n_mb <= 0 || d.n_mb > nmb - next) return JMH_E_INVALID_ARG;
@@ -262,11 +272,56 @@ int jmh_cavlc_run(jmh_cavlc_state **state, const jmh_mb_result *d_res, const jmh
         if (d.lead_nbits < 0 || d.lead_nbits > 7) return JMH_E_INVALID_ARG;
         next += d.n_mb;
     }
-    if (next != nmb) return JMH_E_INVALID_ARG;
+    return next == nmb ? JMH_OK : JMH_E_INVALID_ARG;
+}
+
+// the enqueue half, first part: count and scan.  where / total / ovf are the picture's own (device)
+static int cv_enqueue_count(jmh_cavlc_state *s, const CvPic &p, jmh_slice_bytes *d_where, int64_t *d_total, uint64_t cap_bytes, uint32_t *d_ovf) {
+    const int grid = (p.nmb + CV_WAVES - 1) / CV_WAVES;
+    hipLaunchKernelGGL(k_cavlc_count, dim3(grid), dim3(64 * CV_WAVES), 0, s->st, p, s->d_unit, s->d_bits, s->d_run, s->d_slice);
+    CVCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cavlc_scan, dim3(1), dim3(1024), 0, s->st, p, s->d_bits, s->d_off, d_where, d_total, cap_bytes, d_ovf);
+    CVCHK(hipGetLastError());
+    return JMH_OK;
+}
+// ... second part: the write pass into d_out (zero_bytes of it zeroed first: whole dwords)
+static int cv_enqueue_write(jmh_cavlc_state *s, const CvPic &p, const jmh_slice_bytes *d_where, uint32_t *d_out, size_t zero_bytes,
+                            const uint32_t *d_ovf) {
+    const int grid = (p.nmb + CV_WAVES - 1) / CV_WAVES;
+    CVCHK(hipMemsetAsync(d_out, 0, zero_bytes, s->st));
+    hipLaunchKernelGGL(k_cavlc_write, dim3(grid), dim3(64 * CV_WAVES), 0, s->st, p, s->d_unit, s->d_bits, s->d_run, s->d_slice, s->d_off,
+                       d_where, d_out, (uint64_t)(zero_bytes / 4), d_ovf);
+    CVCHK(hipGetLastError());
+    return JMH_OK;
+}
+
+int jmh_cavlc_enqueue(jmh_cavlc_state **state, const jmh_mb_result *d_res, hipEvent_t after, int mbw, int mbh, int t8mode, int cip, int n,
+                      const jmh_writer_job *job, hipStream_t *stream) {
+    const int nmb = mbw * mbh;
     if (!*state) *state = new jmh_cavlc_state();
     jmh_cavlc_state *s = *state;
     int r = cv_setup(s, nmb, n);
     if (r) return r;
+    *stream = s->st;
+    CVCHK(hipStreamWaitEvent(s->st, after, 0));
+    CVCHK(hipMemcpyAsync(job->d_sl, job->h_sl, (size_t)n * sizeof(jmh_slice_desc), hipMemcpyHostToDevice, s->st));
+    CVCHK(hipMemsetAsync(job->d_meta, 0, JMH_WRITER_META_BYTES, s->st));
+    CvPic p;
+    p.res = d_res; p.mbw = mbw; p.mbh = mbh; p.t8mode = t8mode; p.cip = cip; p.nmb = nmb; p.nslices = n; p.sl = (const jmh_slice_desc *)job->d_sl;
+    uint32_t *ovf = (uint32_t *)(job->d_meta + 1);
+    if ((r = cv_enqueue_count(s, p, (jmh_slice_bytes *)job->d_where, (int64_t *)job->d_meta, (uint64_t)job->out_cap, ovf))) return r;
+    return cv_enqueue_write(s, p, (const jmh_slice_bytes *)job->d_where, (uint32_t *)job->d_out, job->out_cap, ovf);
+}
+
+int jmh_cavlc_run(jmh_cavlc_state **state, const jmh_mb_result *d_res, const jmh_mb_result *h_res, hipEvent_t after, int mbw, int mbh,
+                  int t8mode, int cip, int n, const jmh_slice_desc *slices, uint8_t *out, size_t cap, jmh_slice_bytes *where) {
+    const int nmb = mbw * mbh;
+    if (!where || (!d_res && !h_res)) return JMH_E_INVALID_ARG;
+    int r = jmh_cavlc_check(nmb, n, slices);
+    if (r) return r;
+    if (!*state) *state = new jmh_cavlc_state();
+    jmh_cavlc_state *s = *state;
+    if ((r = cv_setup(s, nmb, n))) return r;
     if (h_res) {
         if (!s->d_res && hipMalloc((void **)&s->d_res, (size_t)nmb * sizeof(jmh_mb_result)) != hipSuccess) return JMH_E_OOM;
         CVCHK(hipMemcpyAsync(s->d_res, h_res, (size_t)nmb * sizeof(jmh_mb_result), hipMemcpyHostToDevice, s->st));
@@ -275,11 +330,8 @@ int jmh_cavlc_run(jmh_cavlc_state **state, const jmh_mb_result *d_res, const jmh
     CVCHK(hipMemcpyAsync(s->d_sl, slices, (size_t)n * sizeof(jmh_slice_desc), hipMemcpyHostToDevice, s->st));
     CvPic p;
     p.res = d_res; p.mbw = mbw; p.mbh = mbh; p.t8mode = t8mode; p.cip = cip; p.nmb = nmb; p.nslices = n; p.sl = s->d_sl;
-    const int grid = (nmb + CV_WAVES - 1) / CV_WAVES;
-    hipLaunchKernelGGL(k_cavlc_count, dim3(grid), dim3(64 * CV_WAVES), 0, s->st, p, s->d_unit, s->d_bits, s->d_run, s->d_slice);
-    CVCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_cavlc_scan, dim3(1), dim3(1024), 0, s->st, p, s->d_bits, s->d_off, s->d_where, s->d_total);
-    CVCHK(hipGetLastError());
+    // the synchronous call sizes its buffer from the count: the host is the collect half between the two enqueues
+    if ((r = cv_enqueue_count(s, p, s->d_where, s->d_total, 0, nullptr))) return r;
     CVCHK(hipMemcpyAsync(s->h_where, s->d_where, (size_t)n * sizeof(jmh_slice_bytes), hipMemcpyDeviceToHost, s->st));
     CVCHK(hipMemcpyAsync(s->h_where + n, s->d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s->st));
     CVCHK(hipStreamSynchronize(s->st));      // the writer's own stream only
@@ -295,10 +347,7 @@ int jmh_cavlc_run(jmh_cavlc_state **state, const jmh_mb_result *d_res, const jmh
         if (hipMalloc((void **)&s->d_out, want) != hipSuccess) return JMH_E_OOM;
         s->out_cap = want;
     }
-    CVCHK(hipMemsetAsync(s->d_out, 0, need, s->st));
-    hipLaunchKernelGGL(k_cavlc_write, dim3(grid), dim3(64 * CV_WAVES), 0, s->st, p, s->d_unit, s->d_bits, s->d_run, s->d_slice, s->d_off,
-                       s->d_where, s->d_out, (uint64_t)(need / 4));
-    CVCHK(hipGetLastError());
+    if ((r = cv_enqueue_write(s, p, s->d_where, s->d_out, need, nullptr))) return r;
     CVCHK(hipMemcpyAsync(out, s->d_out, (size_t)total, hipMemcpyDeviceToHost, s->st));
     CVCHK(hipStreamSynchronize(s->st));
     return JMH_OK;

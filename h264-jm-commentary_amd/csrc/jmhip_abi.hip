@@ -24,6 +24,15 @@
 #include "jmh_cabac.h"
 #include "jmh_cabac_rate.h"
 
+// Coded pictures: bytes of output per macroblock that a picture's writer is queued with, unless
+// JMH_CODED_CAP says otherwise.  192 B per MB is about four times the densest picture recorded
+// under profiles/: the IDR picture of f4_lencod2160_device_cabac.log, 12,675,680 bits over 32,400
+// MBs = 49 B per MB (synthetic source, QP 28; its P pictures stay below 18).  The factor is a
+// margin, not a measurement; a picture that needs more is coded by the synchronous path at its
+// pop and raises the capacity of the pictures pushed after that.
+#define JMH_CODED_CAP_DEFAULT 192
+#define JMW_MB_MAX_BYTES_ANY 16576       // no macroblock needs more: 7 * JMC_MB_MAX_BINS / 8, above JMW_MB_MAX_BITS / 8
+
 // quantisation rounding selector of a slice (q_round, jmh_common.h; docs/JM_SEMANTICS.md items 1
 // and 45): JM 8.6 = 1 in I slices, 0 in P slices; JMVersion >= 10 = 2 + the slice's OffsetMatrix entry
 static int q_selector(const jmh_config &cfg, bool i_slice) {
@@ -99,7 +108,28 @@ struct PicBuf {
     int unpopped;                        // readback picture not yet popped
     int deblocked;                       // the occupant was deblocked on the device (dbk valid)
     uint32_t gen;                        // dataflow: occupants so far (the flag value of its MBs)
+    // coded pictures (jmhip_coded.h): the entry's own writer buffers, on its first coded picture
+    int coded;                           // the occupant is a coded picture: no readback, its writer queued behind it
+    int cd_n, cd_cw, cd_ch;              //   its slices, its crop
+    uint8_t *cd_h, *cd_d;                // pinned / device: descriptors [nmb], where [nmb], meta (CodedLayout)
+    jmh_coded_slice *cd_sl;              // pinned (inside cd_h): the caller's descriptors, for the synchronous fallback
+    uint8_t *cd_out;                     // device: the picture's output region
+    size_t cd_cap;                       //   its bytes
 };
+
+// offsets into PicBuf::cd_h / cd_d (each a multiple of 8)
+struct CodedLayout {
+    size_t sl, where, meta, user, bytes;
+    explicit CodedLayout(size_t nmb) {
+        sl = 0;
+        where = sl + nmb * 24;           // jmh_slice_desc is 20 bytes, jmh_cabac_slice_desc 16
+        meta = where + nmb * sizeof(jmh_slice_bytes);
+        user = meta + JMH_WRITER_META_BYTES;
+        bytes = user + nmb * sizeof(jmh_coded_slice);   // (host only)
+    }
+};
+static_assert(sizeof(jmh_slice_bytes) == sizeof(jmh_cabac_slice_bytes) && sizeof(jmh_slice_desc) <= 24 && sizeof(jmh_cabac_slice_desc) <= 24,
+              "CodedLayout");
 
 // a picture in flight (not yet fully issued)
 struct Flight {
@@ -183,6 +213,9 @@ struct jmh_ctx {
     std::vector<uint32_t> fprof_items;
     jmh_cavlc_state *cavlc = nullptr;    // device CAVLC writer (jmh_cavlc.hip): its own stream, created on first use
     jmh_cabac_state *cabac = nullptr;    // device CABAC writer (jmh_cabac.hip): the same
+    size_t coded_cap = 0;                // coded pictures: bytes of output per macroblock queued with a picture
+    std::vector<void *> coded_retired;   //   outgrown output regions: freed with the context
+    uint8_t *h_coded_pic = nullptr;      //   pinned: jmh_read_recon / jmh_read_deblocked of a coded picture
 };
 
 #define HCHK(x)                                                                  \
@@ -220,9 +253,9 @@ int jmh_device_count(void) {
 }  // extern "C"
 
 static void free_entry(PicBuf &b) {
-    void *dev_bufs[] = {b.src, b.rec, b.dbk, b.mv, b.refidx, b.ipred, b.res, b.scr, b.cab, b.range, b.mbi};
+    void *dev_bufs[] = {b.src, b.rec, b.dbk, b.mv, b.refidx, b.ipred, b.res, b.scr, b.cab, b.range, b.mbi, b.cd_d, b.cd_out};
     for (void *p : dev_bufs) if (p) (void)hipFree(p);
-    void *host_bufs[] = {b.h_res, b.h_src, b.h_rec, b.h_dbk, b.h_rp};
+    void *host_bufs[] = {b.h_res, b.h_src, b.h_rec, b.h_dbk, b.h_rp, b.cd_h};
     for (void *p : host_bufs) if (p) (void)hipHostFree(p);
     hipEvent_t evs[] = {b.ev_src, b.ev_t0, b.ev_done, b.ev_fin, b.ev_rp};
     for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
@@ -345,6 +378,8 @@ void jmh_destroy(jmh_ctx *c) {
     jmh_cavlc_free(c->cavlc);
     jmh_cabac_free(c->cabac);
     for (PicBuf &b : c->ring) free_entry(b);
+    for (void *p : c->coded_retired) (void)hipFree(p);
+    if (c->h_coded_pic) (void)hipHostFree(c->h_coded_pic);
     void *dev_bufs[] = {c->d_ref, c->d_qpel, c->d_slots, c->d_prof, c->d_bprof, c->spic[0].cur, c->spic[0].ref, c->d_ordtab, c->spic[1].cur,
                         c->spic[1].ref, c->d_sched, c->d_soff, c->d_rscr, c->d_ffs, c->d_seg[0], c->d_seg[1], c->d_flags, c->d_head,
                         c->d_fprof};
@@ -437,6 +472,11 @@ int jmh_create(const jmh_config *cfg, int hip_device, jmh_ctx **out) {
     c->next_id = 0; c->next_entry = 0; c->last_id = -1; c->last_entry = -1;
     c->ref_kind = REF_NONE; c->ref_entry = -1; c->cur_entry = -1;
     c->prof_mb = -1;
+    {   // coded pictures: the output bytes per macroblock queued with a picture (the heuristic)
+        const char *e = getenv("JMH_CODED_CAP");
+        c->coded_cap = e && atol(e) > 0 ? (size_t)atol(e) : JMH_CODED_CAP_DEFAULT;
+        if (c->coded_cap > JMW_MB_MAX_BYTES_ANY) c->coded_cap = JMW_MB_MAX_BYTES_ANY;
+    }
     int st = JMH_OK;
 #define ALLOC(p, n) do { if (hipMalloc((void **)&(p), (n)) != hipSuccess) { st = JMH_E_OOM; goto fail; } } while (0)
     {
@@ -726,6 +766,28 @@ static int flow_check(jmh_ctx *c) {
     return JMH_OK;
 }
 
+// A coded picture's last tick (ev_fin recorded): its slice writer and its distortion on the writer's
+// stream, with no host wait between the passes, then where[] and the meta words into pinned memory
+// and the done event.  All of it overlaps the ticks of the pictures still in flight; nothing but
+// these few bytes is copied to the host (the slice bytes follow at the pop, which knows their count)
+static int finish_coded(jmh_ctx *c, const Flight &f, PicBuf &b) {
+    const CodedLayout L(c->nmb);
+    jmh_writer_job job;
+    job.h_sl = b.cd_h + L.sl; job.d_sl = b.cd_d + L.sl; job.d_where = b.cd_d + L.where;
+    job.d_meta = (uint64_t *)(b.cd_d + L.meta); job.d_out = b.cd_out; job.out_cap = b.cd_cap;
+    hipStream_t wst = nullptr;
+    const int t8 = c->cfg.transform_8x8_mode, cip = c->cfg.constrained_intra_pred;
+    int r = c->cfg.symbol_mode ? jmh_cabac_enqueue(&c->cabac, b.res, b.ev_fin, c->mbw, c->mbh, t8, cip, b.cd_n, &job, &wst)
+                               : jmh_cavlc_enqueue(&c->cavlc, b.res, b.ev_fin, c->mbw, c->mbh, t8, cip, b.cd_n, &job, &wst);
+    if (r) return r;
+    if ((r = jmh_plane_ssd(wst, b.src, f.pp.dbk ? b.dbk : b.rec, c->W, c->H, b.cd_cw, b.cd_ch, c->ps, job.d_meta + 2))) return r;
+    HCHK(hipMemcpyAsync(b.cd_h + L.where, b.cd_d + L.where, (size_t)b.cd_n * sizeof(jmh_slice_bytes), hipMemcpyDeviceToHost, wst));
+    HCHK(hipMemcpyAsync(b.cd_h + L.meta, b.cd_d + L.meta, JMH_WRITER_META_BYTES, hipMemcpyDeviceToHost, wst));
+    HCHK(hipEventRecord(b.ev_done, wst));
+    b.recon_read = 0;
+    return JMH_OK;
+}
+
 // after a picture's last tick: its readback on the copy stream (the D2H overlaps the ticks of
 // the pictures still in flight; the entry's device buffers are not written again before the host
 // has popped the picture, which waits for ev_done), then the done event
@@ -736,6 +798,7 @@ static int finish_picture(jmh_ctx *c, const Flight &f) {
     if (r) return r;
     PicBuf &b = c->ring[f.entry];
     HCHK(hipEventRecord(b.ev_fin, c->st));
+    if (b.coded) return finish_coded(c, f, b);
     HCHK(hipStreamWaitEvent(c->cst, b.ev_fin, 0));
     HCHK(hipMemcpyAsync(b.h_res, b.res, c->nmb * sizeof(jmh_mb_result), hipMemcpyDeviceToHost, c->cst));
     b.recon_read = !(f.pp.dbk && (c->cfg.flags & JMH_FLAG_NO_RECON_READBACK));
@@ -902,7 +965,7 @@ static const uint8_t *ref_ptr(const jmh_ctx *c) {
 }
 
 // queue one picture (src: device 4:2:0 picture that stays valid until it is fully issued)
-static int push_picture(jmh_ctx *c, const uint8_t *src, int entry, const jmh_frame_params *fp, bool readback) {
+static int push_picture(jmh_ctx *c, const uint8_t *src, int entry, const jmh_frame_params *fp, int readback) {
     const bool p_slice = fp->slice_type == JMH_P_SLICE;
     PicBuf &b = c->ring[entry];
     Flight f;
@@ -1041,17 +1104,64 @@ int jmh_set_reference_slot(jmh_ctx *c, int slot) {
 }
 
 }  // extern "C"
-static int frame_push_any(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const jmh_frame_params *fp, bool wide) {
+// a coded push: the caller's slices and crop (null: an ordinary picture)
+struct CodedPush { int n; const jmh_coded_slice *sl; int cw, ch; };
+
+// the caller's descriptors as the context's coder takes them, into dst (nmb entries of 24 bytes);
+// JMH_OK when they tile the picture
+static int coded_descs(const jmh_ctx *c, const CodedPush &cp, void *dst) {
+    if (cp.n <= 0 || cp.n > (int)c->nmb || !cp.sl) return JMH_E_INVALID_ARG;
+    if (c->cfg.symbol_mode) {
+        jmh_cabac_slice_desc *d = (jmh_cabac_slice_desc *)dst;
+        for (int i = 0; i < cp.n; i++) { d[i].first_mb = cp.sl[i].first_mb; d[i].n_mb = cp.sl[i].n_mb; d[i].slice_type = cp.sl[i].slice_type; d[i].slice_qp = cp.sl[i].slice_qp; }
+        return jmh_cabac_check((int)c->nmb, cp.n, d);
+    }
+    jmh_slice_desc *d = (jmh_slice_desc *)dst;
+    for (int i = 0; i < cp.n; i++) {
+        d[i].first_mb = cp.sl[i].first_mb; d[i].n_mb = cp.sl[i].n_mb; d[i].slice_type = cp.sl[i].slice_type;
+        d[i].lead_nbits = cp.sl[i].lead_nbits; d[i].lead_bits = cp.sl[i].lead_bits;
+    }
+    return jmh_cavlc_check((int)c->nmb, cp.n, d);
+}
+
+// the entry's writer buffers: once, and an output region of the context's current capacity (an
+// outgrown one is retired, not freed: hipFree would wait for the device)
+static int alloc_coded(jmh_ctx *c, PicBuf &b) {
+    const CodedLayout L(c->nmb);
+    if (!b.cd_h && hipHostMalloc((void **)&b.cd_h, L.bytes, hipHostMallocDefault) != hipSuccess) { b.cd_h = nullptr; return JMH_E_OOM; }
+    if (!b.cd_d && hipMalloc((void **)&b.cd_d, L.user) != hipSuccess) { b.cd_d = nullptr; return JMH_E_OOM; }
+    b.cd_sl = (jmh_coded_slice *)(b.cd_h + L.user);
+    const size_t want = (c->nmb * c->coded_cap + 3) & ~(size_t)3;
+    if (want > b.cd_cap) {
+        if (b.cd_out) c->coded_retired.push_back(b.cd_out);
+        b.cd_out = nullptr; b.cd_cap = 0;
+        if (hipMalloc((void **)&b.cd_out, want) != hipSuccess) { b.cd_out = nullptr; return JMH_E_OOM; }
+        b.cd_cap = want;
+    }
+    return JMH_OK;
+}
+
+static int frame_push_any(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const jmh_frame_params *fp, bool wide,
+                          const CodedPush *cp = nullptr) {
     if (!c || !y || !u || !v || !fp || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
     int r = check_params(c, fp);
     if (r) return r;
     if ((r = check_pic(c, wide))) return r;
+    std::vector<uint8_t> descs;
+    if (cp) {   // before anything is claimed or queued
+        if (cp->cw <= 0 || cp->ch <= 0 || cp->cw > c->W || cp->ch > c->H) return JMH_E_INVALID_ARG;
+        descs.resize(c->nmb * 24);
+        if ((r = coded_descs(c, *cp, descs.data()))) return r;
+    }
     if ((int)c->popq.size() >= c->depth) return JMH_E_STATE;
     HCHK(hipSetDevice(c->dev));
     int e;
     if ((r = claim_entry(c, &e))) return r;
     PicBuf &b = c->ring[e];
-    if ((r = alloc_host(c, b))) return r;
+    if (cp) {   // no readback: the source staging only
+        if (!b.h_src && hipHostMalloc((void **)&b.h_src, c->fsize, hipHostMallocDefault) != hipSuccess) { b.h_src = nullptr; return JMH_E_OOM; }
+        if ((r = alloc_coded(c, b))) return r;
+    } else if ((r = alloc_host(c, b))) return r;
     HCHK(hipEventSynchronize(b.ev_src));   // the previous H2D out of this staging buffer
     // an out-of-range sample rejects the picture before its own copy or ticks are queued: the
     // claimed entry stays free (nothing refers to it).  Not side-effect free: claiming the entry
@@ -1060,8 +1170,15 @@ static int frame_push_any(jmh_ctx *c, const void *y, const void *u, const void *
     HCHK(hipEventRecord(b.ev_t0, c->st));
     HCHK(hipMemcpyAsync(b.src, b.h_src, c->fsize, hipMemcpyHostToDevice, c->st));
     HCHK(hipEventRecord(b.ev_src, c->st));
+    b.coded = cp != nullptr;
+    if (cp) {
+        const CodedLayout L(c->nmb);
+        memcpy(b.cd_h + L.sl, descs.data(), (size_t)cp->n * 24);
+        memcpy(b.cd_sl, cp->sl, (size_t)cp->n * sizeof(jmh_coded_slice));
+        b.cd_n = cp->n; b.cd_cw = cp->cw; b.cd_ch = cp->ch;
+    }
     c->popq.push_back(e);
-    return push_picture(c, b.src, e, fp, true);
+    return push_picture(c, b.src, e, fp, 1);
 }
 extern "C" {
 int jmh_frame_push(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp) {
@@ -1071,11 +1188,20 @@ int jmh_frame_push_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const u
     return frame_push_any(c, y, u, v, sy, sc, fp, true);
 }
 
-int jmh_frame_pop(jmh_ctx *c) {
-    if (!c) return JMH_E_INVALID_ARG;
-    if (c->popq.empty()) return JMH_E_STATE;
-    HCHK(hipSetDevice(c->dev));
-    const int e = c->popq.front();
+int jmh_frame_push_coded(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp, int n,
+                         const jmh_coded_slice *slices, int crop_w, int crop_h) {
+    const CodedPush cp = {n, slices, crop_w, crop_h};
+    return frame_push_any(c, y, u, v, sy, sc, fp, false, &cp);
+}
+int jmh_frame_push_coded_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp,
+                             int n, const jmh_coded_slice *slices, int crop_w, int crop_h) {
+    const CodedPush cp = {n, slices, crop_w, crop_h};
+    return frame_push_any(c, y, u, v, sy, sc, fp, true, &cp);
+}
+
+}  // extern "C"
+// the pop's wait for ring entry e, the oldest picture not yet popped
+static int pop_wait(jmh_ctx *c, int e) {
     int r = issue_while(c, [c, e] {
         for (const Flight &f : c->fl)
             if (f.entry == e) return true;
@@ -1088,12 +1214,77 @@ int jmh_frame_pop(jmh_ctx *c) {
     int ahead = PIPE_LAG;
     if ((r = issue_while(c, [c, &ahead] { return ahead-- > 0 && !c->fl.empty(); }))) return r;
     HCHK(hipEventSynchronize(c->ring[e].ev_done));
-    if ((r = flow_check(c))) return r;
+    return flow_check(c);
+}
+static void pop_done(jmh_ctx *c, int e) {
     c->popq.pop_front();
     c->ring[e].unpopped = 0;
     c->cur_entry = e;
     float ms = 0;
     if (hipEventElapsedTime(&ms, c->ring[e].ev_t0, c->ring[e].ev_done) == hipSuccess) c->timing.total_ms = ms;
+}
+extern "C" {
+int jmh_frame_pop(jmh_ctx *c) {
+    if (!c) return JMH_E_INVALID_ARG;
+    if (c->popq.empty() || c->ring[c->popq.front()].coded) return JMH_E_STATE;   // a coded picture: jmh_frame_pop_coded
+    HCHK(hipSetDevice(c->dev));
+    const int e = c->popq.front();
+    int r = pop_wait(c, e);
+    if (r) return r;
+    pop_done(c, e);
+    return JMH_OK;
+}
+
+int jmh_coded_ring_entries(const jmh_ctx *c) { return c ? c->nring : JMH_E_INVALID_ARG; }
+
+int jmh_frame_pop_coded(jmh_ctx *c, uint8_t *out, size_t cap, jmh_coded_bytes *where, jmh_coded_stats *stats) {
+    if (!c || !where || !stats) return JMH_E_INVALID_ARG;
+    if (c->popq.empty() || !c->ring[c->popq.front()].coded) return JMH_E_STATE;   // an ordinary picture: jmh_frame_pop
+    HCHK(hipSetDevice(c->dev));
+    const int e = c->popq.front();
+    int r = pop_wait(c, e);
+    if (r) return r;
+    PicBuf &b = c->ring[e];
+    const CodedLayout L(c->nmb);
+    const uint64_t *meta = (const uint64_t *)(b.cd_h + L.meta);
+    const bool cabac = c->cfg.symbol_mode != 0;
+    const int n = b.cd_n;
+    const int t8 = c->cfg.transform_8x8_mode, cip = c->cfg.constrained_intra_pred;
+    // where[] of either coder: offset, nbytes, then nbits / nbins
+    const int64_t *w = (const int64_t *)(b.cd_h + L.where);
+    std::vector<int64_t> sync_where;
+    const bool fallback = (uint32_t)meta[1] != 0;
+    if (fallback) {
+        // A counted size exceeded what the picture was queued with, so its passes wrote nothing: the
+        // synchronous writer on the entry's results, which stay until the entry's next occupant
+        sync_where.resize((size_t)n * 3);
+        const void *d = b.cd_h + L.sl;
+        r = cabac ? jmh_cabac_run(&c->cabac, b.res, nullptr, b.ev_done, c->mbw, c->mbh, t8, cip, n, (const jmh_cabac_slice_desc *)d, out, cap,
+                                  (jmh_cabac_slice_bytes *)sync_where.data())
+                  : jmh_cavlc_run(&c->cavlc, b.res, nullptr, b.ev_done, c->mbw, c->mbh, t8, cip, n, (const jmh_slice_desc *)d, out, cap,
+                                  (jmh_slice_bytes *)sync_where.data());
+        if (r && r != JMH_E_INVALID_ARG) return r;
+        w = sync_where.data();
+    }
+    for (int i = 0; i < n; i++) {
+        where[i].offset = w[3 * i]; where[i].nbytes = w[3 * i + 1];
+        where[i].nbits = cabac ? 0 : w[3 * i + 2]; where[i].nbins = cabac ? w[3 * i + 2] : 0;
+    }
+    const int64_t total = where[n - 1].offset + where[n - 1].nbytes;
+    if (fallback) {
+        if (r) return r;                     // cap below the picture's bytes: where[] is filled, the picture stays
+        const size_t need = ((size_t)total * 3 / 2 + c->nmb - 1) / c->nmb;
+        c->coded_cap = std::max(need, std::min(2 * c->coded_cap, (size_t)JMW_MB_MAX_BYTES_ANY));
+    } else {
+        if (total <= 0 || total != (int64_t)meta[0] || (size_t)total > b.cd_cap) return JMH_E_STATE;
+        if (!out || (size_t)total > cap) return JMH_E_INVALID_ARG;
+        // exactly the picture's bytes, on the copy stream: the writer's stream may already hold later pictures
+        HCHK(hipMemcpyAsync(out, b.cd_out, (size_t)total, hipMemcpyDeviceToHost, c->cst));
+        HCHK(hipStreamSynchronize(c->cst));
+    }
+    for (int pl = 0; pl < 3; pl++) stats->ssd[pl] = meta[2 + pl];
+    stats->fallback = fallback; stats->reserved = 0;
+    pop_done(c, e);
     return JMH_OK;
 }
 
@@ -1108,6 +1299,7 @@ int jmh_frame_wait(jmh_ctx *c) { return jmh_frame_pop(c); }
 
 const jmh_mb_result *jmh_get_mb_result(const jmh_ctx *c, int mb_addr) {
     if (!c || c->cur_entry < 0 || mb_addr < 0 || mb_addr >= c->mbw * c->mbh) return nullptr;
+    if (c->ring[c->cur_entry].coded) return nullptr;   // a coded picture's results stay on the device
     return &c->ring[c->cur_entry].h_res[mb_addr];
 }
 
@@ -1150,6 +1342,16 @@ int jmh_cabac_write_results(jmh_ctx *c, const jmh_mb_result *res, int n, const j
 static int read_pic(jmh_ctx *c, void *y, void *u, void *v, int sy, int sc, bool wide, bool dbk) {
     if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
     if ((c->bd > 8) != wide) return JMH_E_UNSUPPORTED_CFG;
+    if (c->cur_entry >= 0 && c->ring[c->cur_entry].coded) {   // not read back at its pop: from the entry's device buffers, on demand
+        const PicBuf &b = c->ring[c->cur_entry];
+        if (dbk && !b.deblocked) return JMH_E_STATE;
+        HCHK(hipSetDevice(c->dev));
+        if (!c->h_coded_pic && hipHostMalloc((void **)&c->h_coded_pic, c->fsize, hipHostMallocDefault) != hipSuccess) { c->h_coded_pic = nullptr; return JMH_E_OOM; }
+        HCHK(hipMemcpyAsync(c->h_coded_pic, dbk ? b.dbk : b.rec, c->fsize, hipMemcpyDeviceToHost, c->cst));
+        HCHK(hipStreamSynchronize(c->cst));
+        unpack_planes(c->h_coded_pic, c->W, c->H, y, u, v, sy, sc, c->ps);
+        return JMH_OK;
+    }
     if (c->cur_entry < 0 || !(dbk ? c->ring[c->cur_entry].deblocked : c->ring[c->cur_entry].recon_read)) return JMH_E_STATE;
     const PicBuf &b = c->ring[c->cur_entry];
     unpack_planes(dbk ? b.h_dbk : b.h_rec, c->W, c->H, y, u, v, sy, sc, c->ps);
@@ -1320,7 +1522,8 @@ int jmh_encode_slot(jmh_ctx *c, int slot, const jmh_frame_params *fp) {
     HCHK(hipSetDevice(c->dev));
     int e;
     if ((r = claim_entry(c, &e))) return r;
-    return push_picture(c, c->d_slots + (size_t)slot * c->fsize, e, fp, false);
+    c->ring[e].coded = 0;
+    return push_picture(c, c->d_slots + (size_t)slot * c->fsize, e, fp, 0);
 }
 
 int jmh_sync(jmh_ctx *c) {

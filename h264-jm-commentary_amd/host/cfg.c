@@ -68,6 +68,7 @@ static const map_entry Map[] = {
     {"WriterThreads", 0, OFF(writer_threads), 0, 64},
     {"DeviceCAVLC", 0, OFF(device_cavlc), 0, 1},
     {"DeviceCABAC", 0, OFF(device_cabac), 0, 1},
+    {"DeviceWriterAsync", 0, OFF(device_writer_async), 0, 1},
     {"JMVersion", 0, OFF(jm_version), 8, 99},
     {"QOffsetIntra", 0, OFF(qoff_intra), -1, JMH_QOFFSET_MAX},
     {"QOffsetInter", 0, OFF(qoff_inter), -1, JMH_QOFFSET_MAX},
@@ -187,6 +188,8 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->device_cabac && !inp->symbol_mode) { snprintf(err, errlen, "DeviceCABAC=1 writes CABAC slice data (SymbolMode=1); with SymbolMode=0 the device writer is DeviceCAVLC=1"); return -1; }
     if (inp->device_cabac && inp->jm_call_surface) { snprintf(err, errlen, "DeviceCABAC=1 replaces the write_one_macroblock loop that JMCallSurface=1 runs (JMCallSurface=0)"); return -1; }
     if (inp->device_cavlc && inp->jm_call_surface) { snprintf(err, errlen, "DeviceCAVLC=1 replaces the write_one_macroblock loop that JMCallSurface=1 runs (JMCallSurface=0)"); return -1; }
+    if (inp->device_writer_async && !inp->device_cavlc && !inp->device_cabac) { snprintf(err, errlen, "DeviceWriterAsync=1 queues the device slice writer behind each picture: it needs DeviceCAVLC=1 (SymbolMode=0) or DeviceCABAC=1 (SymbolMode=1)"); return -1; }
+    if (inp->device_writer_async && inp->pipeline_depth == 1) { snprintf(err, errlen, "DeviceWriterAsync=1 runs the writer under the pictures in flight: it needs the pipelined path (PipelineDepth=0 or > 1)"); return -1; }
     if (inp->symbol_mode && inp->profile_idc == 66) { snprintf(err, errlen, "SymbolMode=1 (CABAC) is not allowed in the Baseline profile (ProfileIDC=66)"); return -1; }
     if (inp->symbol_mode && inp->context_init_method) { snprintf(err, errlen, "ContextInitMethod=1 (adaptive CABAC model selection) not supported (0: FixedModelNumber)"); return -1; }
     if (inp->symbol_mode && inp->model_number) { snprintf(err, errlen, "FixedModelNumber=%d not supported (0: cabac_init_idc 0)", inp->model_number); return -1; }

@@ -39,6 +39,11 @@ double jm_lambda_rdo_on(int qp, int bit_depth, int *lambda_factor) {
 /* squared error summed in integers (per row in 32 bits: 65025 * w < 2^32 for w < 66051; 64-bit
    rows at High 10), so the value equals JM's double accumulation of integer squares exactly; the
    peak is (1 << bit depth) - 1 (JM >= 10 img->max_imgpel_value [J]) */
+double jm_psnr_from_ssd(uint64_t se, int w, int h, int bit_depth) {
+    if (se == 0) return 99.0;
+    const double peak = bit_depth > 8 ? (double)((1 << bit_depth) - 1) : 255.0;
+    return 10.0 * log10(peak * peak * w * h / (double)se);
+}
 static double psnr_pl(const jm_pic *a, const jm_pic *b, int pl, int w, int h) {
     uint64_t se = 0;
     const int st = pl ? a->w / 2 : a->w;
@@ -56,9 +61,7 @@ static double psnr_pl(const jm_pic *a, const jm_pic *b, int pl, int w, int h) {
         }
         se += r;
     }
-    if (se == 0) return 99.0;
-    const double peak = a->bd > 8 ? (double)((1 << a->bd) - 1) : 255.0;
-    return 10.0 * log10(peak * peak * w * h / (double)se);
+    return jm_psnr_from_ssd(se, w, h, a->bd);
 }
 
 /* slice.c › encode_one_slice [J]: the macroblock loop of one slice through the JM 8.6 call
@@ -139,6 +142,13 @@ static jm_cavlc_slices_fn device_cavlc_fn;
 void jm_set_device_cavlc(jm_cavlc_slices_fn fn) { device_cavlc_fn = fn; }
 static jm_cabac_slices_fn device_cabac_fn;
 void jm_set_device_cabac(jm_cabac_slices_fn fn) { device_cabac_fn = fn; }
+/* DeviceWriterAsync 1: the same writers queued behind each pipelined picture (jmh_frame_push_coded /
+ * jmh_frame_pop_coded).  The headers are written when the picture is pushed (device_slice_headers:
+ * frame_num, slice type, QP and first_mb are known then) and kept with the picture; its pop brings
+ * the device bytes, which device_slice_assemble joins to them exactly as the synchronous path does. */
+static jm_coded_push_fn device_coded_push_fn;
+static jm_coded_pop_fn device_coded_pop_fn;
+void jm_set_device_coded(jm_coded_push_fn push, jm_coded_pop_fn pop) { device_coded_push_fn = push; device_coded_pop_fn = pop; }
 
 typedef struct dcavlc {
     int n;                       /* slices per picture */
@@ -147,17 +157,19 @@ typedef struct dcavlc {
     jmh_slice_bytes *where;
     jmh_cabac_slice_desc *cd;
     jmh_cabac_slice_bytes *cwhere;
+    jmh_coded_slice *cs;         /* the descriptors of either coder (the coded push takes these) */
+    jmh_coded_bytes *cw;         /* where of either coder: what device_slice_assemble reads */
     jm_bits *hdr;                /* per slice: the header, then the whole RBSP */
-    uint8_t *buf;
+    uint8_t *buf;                /* the device bytes (NULL in a pending picture's own dcavlc_t: they share one) */
     size_t cap;
 } dcavlc_t;
 
 static void dcavlc_free(dcavlc_t *dc) {
     if (dc->hdr) for (int i = 0; i < dc->n; i++) jm_bits_free(&dc->hdr[i]);
-    free(dc->d); free(dc->where); free(dc->cd); free(dc->cwhere); free(dc->hdr); free(dc->buf);
+    free(dc->d); free(dc->where); free(dc->cd); free(dc->cwhere); free(dc->cs); free(dc->cw); free(dc->hdr); free(dc->buf);
     memset(dc, 0, sizeof(*dc));
 }
-static int dcavlc_init(dcavlc_t *dc, const jm_seq *s, int cabac) {
+static int dcavlc_init(dcavlc_t *dc, const jm_seq *s, int cabac, int with_buf) {
     const int nmb = s->mbw * s->mbh, step = s->slice_mbs > 0 ? s->slice_mbs : nmb;
     memset(dc, 0, sizeof(*dc));
     dc->n = (nmb + step - 1) / step;
@@ -167,18 +179,20 @@ static int dcavlc_init(dcavlc_t *dc, const jm_seq *s, int cabac) {
     dc->cd = (jmh_cabac_slice_desc *)calloc(dc->n, sizeof(*dc->cd));
     dc->cwhere = (jmh_cabac_slice_bytes *)calloc(dc->n, sizeof(*dc->cwhere));
     dc->hdr = (jm_bits *)calloc(dc->n, sizeof(*dc->hdr));
-    dc->cap = (size_t)nmb * 64 + 1024;
-    dc->buf = (uint8_t *)malloc(dc->cap);
-    if (!dc->d || !dc->where || !dc->cd || !dc->cwhere || !dc->hdr || !dc->buf) { dcavlc_free(dc); return JMH_E_OOM; }
+    dc->cs = (jmh_coded_slice *)calloc(dc->n, sizeof(*dc->cs));
+    dc->cw = (jmh_coded_bytes *)calloc(dc->n, sizeof(*dc->cw));
+    dc->cap = with_buf ? (size_t)nmb * 64 + 1024 : 0;
+    dc->buf = with_buf ? (uint8_t *)malloc(dc->cap) : NULL;
+    if (!dc->d || !dc->where || !dc->cd || !dc->cwhere || !dc->cs || !dc->cw || !dc->hdr || (with_buf && !dc->buf)) { dcavlc_free(dc); return JMH_E_OOM; }
     return JMH_OK;
 }
 static int device_call(dcavlc_t *dc, jm_backend *be) {
     return dc->cabac ? device_cabac_fn(be->ctx, dc->n, dc->cd, dc->buf, dc->cap, dc->cwhere)
                      : device_cavlc_fn(be->ctx, dc->n, dc->d, dc->buf, dc->cap, dc->where);
 }
-static int device_picture_slices(dcavlc_t *dc, jm_backend *be, const jm_seq *s, const jm_slice *sl0, jm_bits *out) {
+/* the header / descriptor half: every slice's header into hdr[], its descriptor for either entry point */
+static void device_slice_headers(dcavlc_t *dc, const jm_seq *s, const jm_slice *sl0) {
     const int nmb = s->mbw * s->mbh, step = s->slice_mbs > 0 ? s->slice_mbs : nmb;
-    const long len0 = out->len;
     for (int i = 0; i < dc->n; i++) {
         jm_slice sl = *sl0;
         sl.first_mb = i * step;
@@ -186,8 +200,10 @@ static int device_picture_slices(dcavlc_t *dc, jm_backend *be, const jm_seq *s, 
         h->len = 0; h->acc = 0; h->nacc = 0;
         jm_write_slice_header(h, s, &sl);
         const int n_mb = sl.first_mb + step < nmb ? step : nmb - sl.first_mb;
+        if (dc->cabac) while (h->nacc) jm_put(h, 1, 1);    /* cabac_alignment_one_bit */
+        dc->cs[i].first_mb = sl.first_mb; dc->cs[i].n_mb = n_mb; dc->cs[i].slice_type = sl0->slice_type;
+        dc->cs[i].slice_qp = sl0->qp; dc->cs[i].lead_nbits = h->nacc; dc->cs[i].lead_bits = (uint32_t)h->acc;
         if (dc->cabac) {
-            while (h->nacc) jm_put(h, 1, 1);    /* cabac_alignment_one_bit */
             dc->cd[i].first_mb = sl.first_mb;
             dc->cd[i].n_mb = n_mb;
             dc->cd[i].slice_type = sl0->slice_type;
@@ -200,6 +216,34 @@ static int device_picture_slices(dcavlc_t *dc, jm_backend *be, const jm_seq *s, 
         dc->d[i].lead_nbits = h->nacc;
         dc->d[i].lead_bits = (uint32_t)h->acc;
     }
+}
+/* the assemble half: header bytes + the device bytes that cw[] places in buf, per slice through
+   jm_write_nal; the cabac_zero_words rule on the summed bins */
+static void device_slice_assemble(dcavlc_t *dc, const jm_seq *s, const jm_slice *sl0, const uint8_t *buf, jm_bits *out) {
+    const int nmb = s->mbw * s->mbh;
+    const long len0 = out->len;
+    long bins = 0;
+    for (int i = 0; i < dc->n; i++) {
+        jm_bits *h = &dc->hdr[i];
+        jm_bits t = {(uint8_t *)buf + dc->cw[i].offset, dc->cw[i].nbytes, dc->cw[i].nbytes, 0, 0};
+        h->acc = 0; h->nacc = 0;                /* CAVLC: the partial byte comes back as the first device byte */
+        jm_bits_append(h, &t);
+        jm_write_nal(out, sl0->idr ? 3 : 2, sl0->idr ? 5 : 1, h);
+        if (dc->cabac) bins += (long)dc->cw[i].nbins;
+    }
+    if (dc->cabac) {                            /* cabac_zero_words: as encode_picture_slices */
+        const long bytes = out->len - len0 - 4L * dc->n;
+        const int bd = s->bit_depth > 8 ? s->bit_depth : 8;
+        const long excess = 3 * bins - 36L * bd * nmb - 32 * bytes;
+        for (long z = excess > 0 ? (excess + 95) / 96 : 0; z > 0; z--) {
+            static const uint8_t zw[3] = {0, 0, 3};
+            jm_bits t = {(uint8_t *)zw, 3, 3, 0, 0};
+            jm_bits_append(out, &t);
+        }
+    }
+}
+static int device_picture_slices(dcavlc_t *dc, jm_backend *be, const jm_seq *s, const jm_slice *sl0, jm_bits *out) {
+    device_slice_headers(dc, s, sl0);
     memset(dc->where, 0, dc->n * sizeof(*dc->where));
     memset(dc->cwhere, 0, dc->n * sizeof(*dc->cwhere));
     int r = device_call(dc, be);
@@ -212,28 +256,27 @@ static int device_picture_slices(dcavlc_t *dc, jm_backend *be, const jm_seq *s, 
         r = device_call(dc, be);
     }
     if (r) return r;
-    long bins = 0;
     for (int i = 0; i < dc->n; i++) {
-        jm_bits *h = &dc->hdr[i];
-        const int64_t off = dc->cabac ? dc->cwhere[i].offset : dc->where[i].offset;
-        const int64_t nby = dc->cabac ? dc->cwhere[i].nbytes : dc->where[i].nbytes;
-        jm_bits t = {dc->buf + off, nby, nby, 0, 0};
-        h->acc = 0; h->nacc = 0;                /* CAVLC: the partial byte comes back as the first device byte */
-        jm_bits_append(h, &t);
-        jm_write_nal(out, sl0->idr ? 3 : 2, sl0->idr ? 5 : 1, h);
-        if (dc->cabac) bins += (long)dc->cwhere[i].nbins;
+        dc->cw[i].offset = dc->cabac ? dc->cwhere[i].offset : dc->where[i].offset;
+        dc->cw[i].nbytes = dc->cabac ? dc->cwhere[i].nbytes : dc->where[i].nbytes;
+        dc->cw[i].nbits = dc->cabac ? 0 : dc->where[i].nbits;
+        dc->cw[i].nbins = dc->cabac ? dc->cwhere[i].nbins : 0;
     }
-    if (dc->cabac) {                            /* cabac_zero_words: as encode_picture_slices */
-        const long bytes = out->len - len0 - 4L * dc->n;
-        const int bd = s->bit_depth > 8 ? s->bit_depth : 8;
-        const long excess = 3 * bins - 36L * bd * nmb - 32 * bytes;
-        for (long z = excess > 0 ? (excess + 95) / 96 : 0; z > 0; z--) {
-            static const uint8_t zw[3] = {0, 0, 3};
-            jm_bits t = {(uint8_t *)zw, 3, 3, 0, 0};
-            jm_bits_append(out, &t);
-        }
-    }
+    device_slice_assemble(dc, s, sl0, dc->buf, out);
     return JMH_OK;
+}
+/* DeviceWriterAsync: the pop of the oldest coded picture into the shared buffer of dc (grown to the
+   picture's bytes when the device says so), its where into the picture's own pdc */
+static int device_coded_pop(dcavlc_t *dc, dcavlc_t *pdc, jm_backend *be, jmh_coded_stats *stats) {
+    int r = device_coded_pop_fn(be->ctx, dc->buf, dc->cap, pdc->cw, stats);
+    const size_t total = (size_t)(pdc->cw[pdc->n - 1].offset + pdc->cw[pdc->n - 1].nbytes);
+    if (r == JMH_E_INVALID_ARG && total > dc->cap) {
+        uint8_t *nb = (uint8_t *)realloc(dc->buf, 2 * total);
+        if (!nb) return JMH_E_OOM;
+        dc->buf = nb; dc->cap = 2 * total;
+        r = device_coded_pop_fn(be->ctx, dc->buf, dc->cap, pdc->cw, stats);
+    }
+    return r;
 }
 
 /* ---- parallel slice writing (WriterThreads > 0, pipelined device backend) -------------------
@@ -343,6 +386,10 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         return JMH_E_UNSUPPORTED_CFG;
     }
     const int device_writer = inp->device_cavlc || inp->device_cabac;
+    if (inp->device_writer_async && !(device_coded_push_fn && device_coded_pop_fn)) {
+        fprintf(stderr, "DeviceWriterAsync=1 needs the device backend (backend '%s' has no coded push / pop: DeviceWriterAsync=0)\n", be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     jmh_config cfg;
     jm_fill_config(inp, &cfg);
     int W = cfg.width, H = cfg.height;
@@ -378,6 +425,14 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     const int dev_dbk = be->read_deblocked && be->reference_deblocked;
     const int pipelined = dev_dbk && be->push && be->pop && be->depth > 1;
     const int depth = pipelined ? be->depth : 1;
+    const int async = inp->device_writer_async;
+    if (async && !pipelined) {
+        fprintf(stderr, "DeviceWriterAsync=1 needs the pipelined path (device deblocking, more than one picture in flight)\n");
+        if (fin) fclose(fin);
+        fclose(fout);
+        if (frec) fclose(frec);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     /* parallel slice writing: pipelined device backend, not with the call surface's per-MB
        device searches (those share the context with the frame loop) */
     const int nwr = (pipelined && !inp->jm_call_surface && !device_writer) ? inp->writer_threads : 0;
@@ -406,6 +461,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     memset(&pool, 0, sizeof(pool));
     dcavlc_t dc;
     memset(&dc, 0, sizeof(dc));
+    dcavlc_t *pdc = NULL;        /* DeviceWriterAsync: per pending picture, its headers and descriptors */
     int st_ret = 0, njobs_init = 0, nstarted = 0, pool_sync = 0;
     long jseq = 0, jflushed = 0;   /* jobs submitted / emitted (picture order) */
     double copy_ms = 0, write_ms = 0;
@@ -413,7 +469,12 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     jm_bits out, rbsp;
     jm_bits_init(&out); jm_bits_init(&rbsp);
     if (!res || jm86_init(&im, inp, be, W, H)) { st_ret = JMH_E_OOM; goto cleanup; }
-    if (device_writer && dcavlc_init(&dc, &s, inp->device_cabac)) { st_ret = JMH_E_OOM; goto cleanup; }
+    if (device_writer && dcavlc_init(&dc, &s, inp->device_cabac, 1)) { st_ret = JMH_E_OOM; goto cleanup; }
+    if (async) {
+        if (!(pdc = (dcavlc_t *)calloc(plen, sizeof(*pdc)))) { st_ret = JMH_E_OOM; goto cleanup; }
+        for (int k = 0; k < plen; k++)
+            if (dcavlc_init(&pdc[k], &s, inp->device_cabac, 0)) { st_ret = JMH_E_OOM; goto cleanup; }
+    }
     if (nwr) {
         pool.nj = nj; pool.s = &s; pool.inp = inp; pool.nth = nwr;
         pool.jobs = (wjob_t *)calloc(nj, sizeof(wjob_t));
@@ -446,6 +507,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         if (nwr) fprintf(log, " (%d slice-writer threads)\n", nwr);
         if (inp->device_cavlc) fprintf(log, " (CAVLC slice data written on the device)\n");
         if (inp->device_cabac) fprintf(log, " (CABAC slice data written on the device: no writer threads, no per-macroblock rate check)\n");
+        if (async) fprintf(log, " (the slice writer is queued behind each picture: its pop returns the slice bytes and the SSDs)\n");
         fprintf(log, " Frame  Bit/pic  QP   SnrY    SnrU    SnrV    Time(ms) MET(ms) Frm/Fld  I D\n");
     }
     double t_start = now_ms();
@@ -535,15 +597,56 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             fprintf(log, "%4d(%s) %8ld   %2d %7.4f %7.4f %7.4f %9.1f %7.1f    FRM\n", p_->f,          \
                     p_->is_i ? "IDR" : " P ", pic_bits, p_->fp.qp, py, pu, pv, t3 - t1 + (MET_MS), (MET_MS)); \
     } while (0)
+    #define PEND_SLICE(P, SL)                                                                      \
+    do {                                                                                           \
+        (SL).idr = (P)->f == 0; (SL).slice_type = (P)->fp.slice_type; (SL).frame_num = (P)->frame_num; \
+        (SL).poc_lsb = 2 * (P)->f; (SL).idr_pic_id = 0; (SL).qp = (P)->fp.qp; (SL).first_mb = 0;      \
+    } while (0)
+    /* DeviceWriterAsync: the oldest picture's slice bytes and SSDs; headers + bytes to the stream, the
+       PSNR from the SSDs, the picture itself only for the recon file */
+    #define EMIT_CODED(SLOT, MET_MS)                                                               \
+    do {                                                                                           \
+        pend_t *p_ = &pend[(SLOT)];                                                                \
+        double t1 = now_ms();                                                                      \
+        jm_slice sl;                                                                               \
+        PEND_SLICE(p_, sl);                                                                        \
+        device_slice_assemble(&pdc[(SLOT)], &s, &sl, dc.buf, &out);                                \
+        double t2 = now_ms();                                                                      \
+        st->entropy_ms += t2 - t1;                                                                 \
+        long pic_bits = out.len * 8;                                                               \
+        fwrite(out.buf, 1, out.len, fout);                                                         \
+        out.len = 0;                                                                               \
+        if (frec) {                                                                                \
+            int r_ = be->read_deblocked(be->ctx, &rec);                                            \
+            if (r_) { fprintf(stderr, "read_deblocked failed: %d\n", r_); st_ret = r_; break; }    \
+            jm_write_yuv_frame(frec, &rec, inp->width, inp->height);                               \
+        }                                                                                          \
+        double t3 = now_ms();                                                                      \
+        st->deblock_ms += t3 - t2;                                                                 \
+        double py = jm_psnr_from_ssd(cstats.ssd[0], inp->width, inp->height, bd);                  \
+        double pu = jm_psnr_from_ssd(cstats.ssd[1], inp->width / 2, inp->height / 2, bd);          \
+        double pv = jm_psnr_from_ssd(cstats.ssd[2], inp->width / 2, inp->height / 2, bd);          \
+        st->psnr_y += py; st->psnr_u += pu; st->psnr_v += pv;                                      \
+        st->bits += pic_bits;                                                                      \
+        st->frames++;                                                                              \
+        coded_fallbacks += cstats.fallback;                                                        \
+        if (log)                                                                                   \
+            fprintf(log, "%4d(%s) %8ld   %2d %7.4f %7.4f %7.4f %9.1f %7.1f    FRM\n", p_->f,          \
+                    p_->is_i ? "IDR" : " P ", pic_bits, p_->fp.qp, py, pu, pv, t3 - t1 + (MET_MS), (MET_MS)); \
+    } while (0)
+    jmh_coded_stats cstats;
+    memset(&cstats, 0, sizeof(cstats));
+    int coded_fallbacks = 0;
     for (int f = 0; f < inp->frames && !st_ret; f++) {
         if (pipelined && count == depth) {   /* the oldest picture's results */
             double t0 = now_ms();
-            int r = be->pop(be->ctx);
+            int r = async ? device_coded_pop(&dc, &pdc[head], be, &cstats) : be->pop(be->ctx);
             double met = now_ms() - t0;
             if (r) { fprintf(stderr, "hot path backend '%s' failed: status %d\n", be->name, r); st_ret = r; break; }
             st->me_tq_ms += met;
             pop_ms += met;
-            EMIT(&pend[head], met);
+            if (async) EMIT_CODED(head, met);
+            else EMIT(&pend[head], met);
             if (st_ret) break;
             head = (head + 1) % plen;
             count--;
@@ -573,6 +676,13 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         double t0 = now_ms();
         int r = 0;
         if (dev_dbk && !p->is_i) r = be->reference_deblocked(be->ctx);   /* previous picture, on the device */
+        if (!r && async) {   /* the slice headers now: everything they carry is known at the push */
+            dcavlc_t *d = &pdc[(head + count) % plen];
+            jm_slice sl;
+            PEND_SLICE(p, sl);
+            device_slice_headers(d, &s, &sl);
+            r = device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
+        } else
         if (!r) r = pipelined ? be->push(be->ctx, &p->cur, fp) : be->encode_frame(be->ctx, &p->cur, fp);
         double met = now_ms() - t0;
         if (r) { fprintf(stderr, "hot path backend '%s' failed: status %d\n", be->name, r); st_ret = r; break; }
@@ -583,16 +693,21 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     }
     while (pipelined && count && !st_ret) {
         double t0 = now_ms();
-        int r = be->pop(be->ctx);
+        int r = async ? device_coded_pop(&dc, &pdc[head], be, &cstats) : be->pop(be->ctx);
         double met = now_ms() - t0;
         if (r) { fprintf(stderr, "hot path backend '%s' failed: status %d\n", be->name, r); st_ret = r; break; }
         st->me_tq_ms += met;
-        EMIT(&pend[head], met);
+        if (async) EMIT_CODED(head, met);
+        else EMIT(&pend[head], met);
         head = (head + 1) % plen;
         count--;
     }
     while (nwr && jflushed < jseq && !st_ret) FLUSH_JOB(&pool.jobs[jflushed % nj]);
+    if (log && async && coded_fallbacks)
+        fprintf(log, " (%d pictures exceeded the writer's queued capacity and were coded by the synchronous call)\n", coded_fallbacks);
     #undef EMIT
+    #undef EMIT_CODED
+    #undef PEND_SLICE
     #undef SUBMIT
     #undef FLUSH_JOB
     st->total_ms = now_ms() - t_start;
@@ -614,6 +729,8 @@ cleanup:
     }
     free(pool.jobs); free(pool.queue); free(pool.th);
     dcavlc_free(&dc);
+    if (pdc) for (int k = 0; k < plen; k++) dcavlc_free(&pdc[k]);
+    free(pdc);
     img = &im;
     st->surface_checked = im.surface_checked;
     st->surface_searches = im.surface_searches;

@@ -77,6 +77,10 @@ typedef struct jm_input {
                                   and the NAL packaging.  SymbolMode 0, device backend only        */
     int  device_cabac;         /* (this build) DeviceCABAC 1: the same for CABAC slice data (jmh_cabac
                                   _write_slices).  SymbolMode 1, device backend only               */
+    int  device_writer_async;  /* (this build) DeviceWriterAsync 1: with DeviceCAVLC / DeviceCABAC 1 the slice
+                                  writer is queued behind each pipelined picture (jmh_frame_push_coded /
+                                  jmh_frame_pop_coded); the pop returns the slice bytes and the SSDs, no
+                                  results or pictures cross to the host (ReconFile: the picture on demand) */
     int  verbose;
 } jm_input;
 
@@ -233,6 +237,15 @@ void jm_set_device_cavlc(jm_cavlc_slices_fn fn);
 typedef int (*jm_cabac_slices_fn)(void *ctx, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap,
                                   jmh_cabac_slice_bytes *where);
 void jm_set_device_cabac(jm_cabac_slices_fn fn);
+/* DeviceWriterAsync 1: the backend's coded push / pop (jmh_frame_push_coded / jmh_frame_pop_coded,
+   include/jmhip_coded.h); unset on a backend without them, where the key is rejected */
+typedef int (*jm_coded_push_fn)(void *ctx, const jm_pic *cur, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
+                                int crop_w, int crop_h);
+typedef int (*jm_coded_pop_fn)(void *ctx, uint8_t *out, size_t cap, jmh_coded_bytes *where, jmh_coded_stats *stats);
+void jm_set_device_coded(jm_coded_push_fn push, jm_coded_pop_fn pop);
+/* 10 log10(peak^2 w h / ssd) with psnr_pl's arithmetic (99.0 at ssd 0): the PSNR of a w x h plane of
+   bit_depth-bit samples from its summed squared error */
+double jm_psnr_from_ssd(uint64_t ssd, int w, int h, int bit_depth);
 
 typedef struct jm_stats {
     int frames;

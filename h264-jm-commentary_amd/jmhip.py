@@ -203,6 +203,59 @@ def cabac_slice_descs(nmb, slice_type, qp, mbs_per_slice=0):
     return d
 
 
+# ---- coded pictures (include/jmhip_coded.h; additive to ABI 14) ----
+class JmhCodedSlice(ctypes.Structure):
+    _fields_ = [("first_mb", ctypes.c_int32), ("n_mb", ctypes.c_int32), ("slice_type", ctypes.c_int32), ("slice_qp", ctypes.c_int32),
+                ("lead_nbits", ctypes.c_int32), ("lead_bits", ctypes.c_uint32)]
+
+
+class JmhCodedBytes(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("nbytes", ctypes.c_int64), ("nbits", ctypes.c_int64), ("nbins", ctypes.c_int64)]
+
+
+class JmhCodedStats(ctypes.Structure):
+    _fields_ = [("ssd", ctypes.c_uint64 * 3), ("fallback", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+_SIGS_CODED = {
+    "jmh_frame_push_coded": (_I, [_P, _P, _P, _P, _I, _I, ctypes.POINTER(JmhFrameParams), _I, _P, _I, _I]),
+    "jmh_frame_push_coded_u16": (_I, [_P, _P, _P, _P, _I, _I, ctypes.POINTER(JmhFrameParams), _I, _P, _I, _I]),
+    "jmh_frame_pop_coded": (_I, [_P, _P, ctypes.c_size_t, _P, _P]),
+    "jmh_coded_ring_entries": (_I, [_P]),
+}
+EXPORTED_CODED = tuple(_SIGS_CODED)
+
+
+def coded_slice_descs(nmb, slice_type, qp, mbs_per_slice=0, lead=()):
+    """The descriptors of a coded picture (a JmhCodedSlice array), from the two writers' helpers:
+    the raster runs and lead bits of slice_descs, the slice QPs of cabac_slice_descs."""
+    a, b = slice_descs(nmb, slice_type, mbs_per_slice, lead), cabac_slice_descs(nmb, slice_type, qp, mbs_per_slice)
+    d = (JmhCodedSlice * len(a))()
+    for i, (x, y) in enumerate(zip(a, b)):
+        d[i] = JmhCodedSlice(x.first_mb, x.n_mb, x.slice_type, y.slice_qp, x.lead_nbits, x.lead_bits)
+    return d
+
+
+def coded_from_runs(runs, slice_type, qp, lead=()):
+    """The same for slices of the given macroblock counts (raster runs in order)."""
+    d = (JmhCodedSlice * len(runs))()
+    first = 0
+    for i, n in enumerate(runs):
+        nb, bits = lead[i % len(lead)] if lead else (0, 0)
+        d[i] = JmhCodedSlice(first, n, slice_type, qp, nb, bits & ((1 << nb) - 1))
+        first += n
+    return d
+
+
+def split_coded(descs):
+    """A JmhCodedSlice array as the synchronous writers take it: (JmhSliceDesc array, JmhCabacSliceDesc array)."""
+    a, b = (JmhSliceDesc * len(descs))(), (JmhCabacSliceDesc * len(descs))()
+    for i, d in enumerate(descs):
+        a[i] = JmhSliceDesc(d.first_mb, d.n_mb, d.slice_type, d.lead_nbits, d.lead_bits)
+        b[i] = JmhCabacSliceDesc(d.first_mb, d.n_mb, d.slice_type, d.slice_qp)
+    return a, b
+
+
 class JmhError(RuntimeError):
     status = None                # the JMH_E_* code, where a jmh_* call failed
 
@@ -218,7 +271,7 @@ def load(path=LIB_PATH):
     if not os.path.exists(path):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -348,6 +401,53 @@ class Encoder:
         """Wait for the oldest pushed picture; returns (results, recon)."""
         _check(self.lib.jmh_frame_pop(self.ctx), "jmh_frame_pop")
         return self.results(), self.recon()
+
+    # ---- coded pictures (jmh_frame_push_coded / jmh_frame_pop_coded) ----
+    def push_coded(self, y, u, v, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0):
+        """jmh_frame_push with the picture's slices (a JmhCodedSlice array, see coded_slice_descs): its
+        slice data is written on the device behind its last macroblock.  crop: (width, height) of
+        the distortion sums, default the coded size."""
+        fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
+        y, u, v = self._planes(y, u, v)
+        cw, ch = crop if crop is not None else (self.w, self.h)
+        self._coded_n = getattr(self, "_coded_n", [])
+        fn = "jmh_frame_push_coded" + self.sfx
+        _check(getattr(self.lib, fn)(self.ctx, _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2, ctypes.byref(fp), len(descs),
+                                     ctypes.cast(descs, _P), cw, ch), fn)
+        self._coded_n.append(len(descs))
+
+    @property
+    def ring_entries(self):
+        return self.lib.jmh_coded_ring_entries(self.ctx)
+
+    def pop_coded(self, cap=None):
+        """The oldest pushed picture, a coded one: (bytes per slice, [(offset, nbytes, nbits, nbins)],
+        {"ssd": (Y, U, V), "fallback": 0 / 1}).  cap: the size of the output buffer; a picture that
+        needs more raises JmhError (status JMH_E_INVALID_ARG, .where filled) and stays poppable.
+        Without cap the buffer grows to the picture's bytes and the pop is repeated."""
+        if not getattr(self, "_coded_n", None):
+            # no coded picture was pushed: let the library answer (JMH_E_STATE)
+            w1, s1 = (JmhCodedBytes * 1)(), JmhCodedStats()
+            _check(self.lib.jmh_frame_pop_coded(self.ctx, None, 0, ctypes.cast(w1, _P), ctypes.byref(s1)), "jmh_frame_pop_coded")
+        n = self._coded_n[0]
+        where, stats = (JmhCodedBytes * n)(), JmhCodedStats()
+        size = cap if cap is not None else self.mbw * self.mbh * 64
+        while True:
+            out = np.zeros(max(size, 1), np.uint8)
+            st = self.lib.jmh_frame_pop_coded(self.ctx, _ptr(out), size, ctypes.cast(where, _P), ctypes.byref(stats))
+            total = where[n - 1].offset + where[n - 1].nbytes
+            if st == JMH_E_INVALID_ARG and cap is None and total > size:
+                size = total
+                continue
+            break
+        wl = [(w.offset, w.nbytes, w.nbits, w.nbins) for w in where]
+        if st != JMH_OK:
+            e = JmhError(f"jmh_frame_pop_coded: {STATUS.get(st, st)} ({st})")
+            e.status, e.where = st, wl
+            raise e
+        self._coded_n.pop(0)
+        data = [out[w.offset:w.offset + w.nbytes].tobytes() for w in where]
+        return data, wl, {"ssd": tuple(int(x) for x in stats.ssd), "fallback": int(stats.fallback)}
 
     def pop_into(self, y, u, v):
         """What lencod does per picture: jmh_frame_pop, the results in place (a zero-copy view of the

@@ -35,6 +35,9 @@
  * SymbolMode 0): include/jmhip_cavlc.h, included at the end of this file.  It is additive:
  * JMH_ABI_VERSION stays 14 and no struct or entry point declared here changes.  The same for
  * SymbolMode 1 (CABAC): include/jmhip_cabac.h, included behind it, additive as well.
+ * Coded pictures (a pipelined picture whose slice data is written behind its last macroblock and
+ * whose pop returns the slice bytes and the distortion only): include/jmhip_coded.h, included
+ * last, additive as well.
  *
  * Conventions: plain C types only; 0 = OK, negative JMH_E_* on error; nothing throws or aborts
  * across this boundary.  One context = one HIP device + one HIP stream; a context is not
@@ -375,4 +378,5 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #endif
 #include "jmhip_cavlc.h"
 #include "jmhip_cabac.h"
+#include "jmhip_coded.h"
 #endif /* JMHIP_H */
