@@ -299,6 +299,8 @@ struct jmh_cabac_state {
     uint8_t *d_scratch = nullptr, *d_out = nullptr;
     size_t scratch_cap = 0, out_cap = 0;   // bytes
     std::vector<void *> retired;           // outgrown buffers: freed with the state (hipFree would wait for the device)
+    jmh_split_state *split = nullptr;      // the split coder's buffers (jmh_cabac_split.hip), created on first use
+    jmh_cabac_split_info last = {};        // what the last synchronous call did
 };
 
 #define CBCHK(x)                                                                  \
@@ -310,6 +312,10 @@ struct jmh_cabac_state {
         }                                                                         \
     } while (0)
 
+void jmh_cabac_split_last(const jmh_cabac_state *s, jmh_cabac_split_info *out) {
+    *out = s ? s->last : jmh_cabac_split_info{};
+}
+
 void jmh_cabac_free(jmh_cabac_state *s) {
     if (!s) return;
     if (s->st) (void)hipStreamSynchronize(s->st);
@@ -318,6 +324,7 @@ void jmh_cabac_free(jmh_cabac_state *s) {
     for (void *p : bufs) if (p) (void)hipFree(p);
     for (void *p : s->retired) (void)hipFree(p);
     if (s->h_where) (void)hipHostFree(s->h_where);
+    jmh_split_free(s->split);
     if (s->st) (void)hipStreamDestroy(s->st);
     delete s;
 }
@@ -377,14 +384,21 @@ static int cb_enqueue_count(jmh_cabac_state *s, const CbPic &p, uint64_t *d_tota
     CBCHK(hipGetLastError());
     return JMH_OK;
 }
+// chunk_bins > 0: the split coder's launches stand in k_cabac_code's place; nbins > 0: the picture's counted bins
 static int cb_enqueue_code(jmh_cabac_state *s, const CbPic &p, jmh_cabac_slice_bytes *d_where, int64_t *d_total, uint64_t out_cap,
-                           uint32_t *d_ovf) {
+                           uint32_t *d_ovf, int chunk_bins, uint64_t nbins) {
     const int grid = (p.nmb + CB_WAVES - 1) / CB_WAVES;
     hipLaunchKernelGGL(k_cabac_bins, dim3(grid), dim3(64 * CB_WAVES), 0, s->st, p, s->d_unit, s->d_slice, s->d_off, s->d_rec,
                        (uint64_t)(s->rec_cap / sizeof(uint16_t)), d_ovf);
     CBCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_cabac_code, dim3(p.nslices), dim3(64), 0, s->st, p, s->d_off, s->d_soff, s->d_rec, s->d_scratch, s->d_slbytes, d_ovf);
-    CBCHK(hipGetLastError());
+    if (chunk_bins > 0) {
+        const int r = jmh_split_enqueue(&s->split, s->st, p.sl, p.nslices, s->d_off, s->d_soff, s->d_rec,
+                                        (uint64_t)(s->rec_cap / sizeof(uint16_t)), s->d_scratch, s->d_slbytes, d_ovf, chunk_bins, nbins != 0);
+        if (r) return r;
+    } else {
+        hipLaunchKernelGGL(k_cabac_code, dim3(p.nslices), dim3(64), 0, s->st, p, s->d_off, s->d_soff, s->d_rec, s->d_scratch, s->d_slbytes, d_ovf);
+        CBCHK(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_cabac_where, dim3(1), dim3(1024), 0, s->st, p, s->d_off, s->d_slbytes, d_where, d_total, out_cap, d_ovf);
     CBCHK(hipGetLastError());
     return JMH_OK;
@@ -401,7 +415,7 @@ static int cb_enqueue_pack(jmh_cabac_state *s, int n, const jmh_cabac_slice_byte
 // holds every slice's bound for that many bins
 #define JMH_CODED_BINS_PER_BYTE 10
 int jmh_cabac_enqueue(jmh_cabac_state **state, const jmh_mb_result *d_res, hipEvent_t after, int mbw, int mbh, int t8mode, int cip, int n,
-                      const jmh_writer_job *job, hipStream_t *stream) {
+                      const jmh_writer_job *job, hipStream_t *stream, int chunk_bins) {
     const int nmb = mbw * mbh;
     if (!*state) *state = new jmh_cabac_state();
     jmh_cabac_state *s = *state;
@@ -420,13 +434,15 @@ int jmh_cabac_enqueue(jmh_cabac_state **state, const jmh_mb_result *d_res, hipEv
     p.sl = (const jmh_cabac_slice_desc *)job->d_sl;
     uint32_t *ovf = (uint32_t *)(job->d_meta + 1);
     if ((r = cb_enqueue_count(s, p, job->d_meta + 5, (uint64_t)(s->rec_cap / sizeof(uint16_t)), (uint64_t)s->scratch_cap, ovf))) return r;
-    if ((r = cb_enqueue_code(s, p, (jmh_cabac_slice_bytes *)job->d_where, (int64_t *)job->d_meta, (uint64_t)job->out_cap, ovf))) return r;
+    if ((r = cb_enqueue_code(s, p, (jmh_cabac_slice_bytes *)job->d_where, (int64_t *)job->d_meta, (uint64_t)job->out_cap, ovf, chunk_bins, 0))) return r;
     return cb_enqueue_pack(s, n, (const jmh_cabac_slice_bytes *)job->d_where, job->d_out, (uint64_t)job->out_cap, ovf);
 }
 
 int jmh_cabac_run(jmh_cabac_state **state, const jmh_mb_result *d_res, const jmh_mb_result *h_res, hipEvent_t after, int mbw, int mbh,
-                  int t8mode, int cip, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap, jmh_cabac_slice_bytes *where) {
+                  int t8mode, int cip, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap, jmh_cabac_slice_bytes *where,
+                  int chunk_bins) {
     const int nmb = mbw * mbh;
+    if (*state) (*state)->last = jmh_cabac_split_info{};
     if (!where || (!d_res && !h_res)) return JMH_E_INVALID_ARG;
     int r = jmh_cabac_check(nmb, n, slices);
     if (r) return r;
@@ -449,10 +465,15 @@ int jmh_cabac_run(jmh_cabac_state **state, const jmh_mb_result *d_res, const jmh
     if (nbins == 0 || nbins > (uint64_t)nmb * JMC_MB_MAX_BINS) return JMH_E_STATE;   // the documented bound
     if ((r = cb_grow(s, (void **)&s->d_rec, &s->rec_cap, (size_t)nbins * sizeof(uint16_t), (size_t)nmb * 256))) return r;
     if ((r = cb_grow(s, (void **)&s->d_scratch, &s->scratch_cap, (size_t)nscratch, (size_t)nmb * 128))) return r;
-    if ((r = cb_enqueue_code(s, p, s->d_where, s->d_total, 0, nullptr))) return r;
+    if ((r = cb_enqueue_code(s, p, s->d_where, s->d_total, 0, nullptr, chunk_bins, nbins))) return r;
     CBCHK(hipMemcpyAsync(s->h_where, s->d_where, (size_t)n * sizeof(jmh_cabac_slice_bytes), hipMemcpyDeviceToHost, s->st));
     CBCHK(hipMemcpyAsync(s->h_where + nmb, s->d_total, sizeof(int64_t), hipMemcpyDeviceToHost, s->st));
     CBCHK(hipStreamSynchronize(s->st));
+    if (chunk_bins > 0) {
+        const uint64_t *t = jmh_split_totals(s->split);
+        s->last.chunk_bins = chunk_bins; s->last.chunks = (int64_t)t[0]; s->last.longest_slice_chunks = (int64_t)t[2];
+        s->last.scratch_bytes = (int64_t)jmh_split_bytes(s->split);
+    }
     const int64_t total = s->h_where[nmb].offset;
     if (total <= 0 || (uint64_t)total > nscratch) return JMH_E_STATE;
     memcpy(where, s->h_where, (size_t)n * sizeof(jmh_cabac_slice_bytes));

@@ -212,6 +212,7 @@ struct jmh_ctx {
     size_t fprof_n = 0;
     std::vector<uint32_t> fprof_items;
     jmh_cavlc_state *cavlc = nullptr;    // device CAVLC writer (jmh_cavlc.hip): its own stream, created on first use
+    int cabac_split = 0;                 // jmh_cabac_set_split: bins per chunk of the split coder, 0 off
     jmh_cabac_state *cabac = nullptr;    // device CABAC writer (jmh_cabac.hip): the same
     size_t coded_cap = 0;                // coded pictures: bytes of output per macroblock queued with a picture
     std::vector<void *> coded_retired;   //   outgrown output regions: freed with the context
@@ -777,7 +778,7 @@ static int finish_coded(jmh_ctx *c, const Flight &f, PicBuf &b) {
     job.d_meta = (uint64_t *)(b.cd_d + L.meta); job.d_out = b.cd_out; job.out_cap = b.cd_cap;
     hipStream_t wst = nullptr;
     const int t8 = c->cfg.transform_8x8_mode, cip = c->cfg.constrained_intra_pred;
-    int r = c->cfg.symbol_mode ? jmh_cabac_enqueue(&c->cabac, b.res, b.ev_fin, c->mbw, c->mbh, t8, cip, b.cd_n, &job, &wst)
+    int r = c->cfg.symbol_mode ? jmh_cabac_enqueue(&c->cabac, b.res, b.ev_fin, c->mbw, c->mbh, t8, cip, b.cd_n, &job, &wst, c->cabac_split)
                                : jmh_cavlc_enqueue(&c->cavlc, b.res, b.ev_fin, c->mbw, c->mbh, t8, cip, b.cd_n, &job, &wst);
     if (r) return r;
     if ((r = jmh_plane_ssd(wst, b.src, f.pp.dbk ? b.dbk : b.rec, c->W, c->H, b.cd_cw, b.cd_ch, c->ps, job.d_meta + 2))) return r;
@@ -1260,7 +1261,7 @@ int jmh_frame_pop_coded(jmh_ctx *c, uint8_t *out, size_t cap, jmh_coded_bytes *w
         sync_where.resize((size_t)n * 3);
         const void *d = b.cd_h + L.sl;
         r = cabac ? jmh_cabac_run(&c->cabac, b.res, nullptr, b.ev_done, c->mbw, c->mbh, t8, cip, n, (const jmh_cabac_slice_desc *)d, out, cap,
-                                  (jmh_cabac_slice_bytes *)sync_where.data())
+                                  (jmh_cabac_slice_bytes *)sync_where.data(), c->cabac_split)
                   : jmh_cavlc_run(&c->cavlc, b.res, nullptr, b.ev_done, c->mbw, c->mbh, t8, cip, n, (const jmh_slice_desc *)d, out, cap,
                                   (jmh_slice_bytes *)sync_where.data());
         if (r && r != JMH_E_INVALID_ARG) return r;
@@ -1328,14 +1329,29 @@ int jmh_cabac_write_slices(jmh_ctx *c, int n, const jmh_cabac_slice_desc *slices
     HCHK(hipSetDevice(c->dev));
     const PicBuf &b = c->ring[c->cur_entry];
     return jmh_cabac_run(&c->cabac, b.res, nullptr, b.ev_done, c->mbw, c->mbh, c->cfg.transform_8x8_mode, c->cfg.constrained_intra_pred, n,
-                         slices, out, cap, where);
+                         slices, out, cap, where, c->cabac_split);
 }
 int jmh_cabac_write_results(jmh_ctx *c, const jmh_mb_result *res, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap,
                             jmh_cabac_slice_bytes *where) {
     if (!c || !res) return JMH_E_INVALID_ARG;
     HCHK(hipSetDevice(c->dev));
     return jmh_cabac_run(&c->cabac, nullptr, res, nullptr, c->mbw, c->mbh, c->cfg.transform_8x8_mode, c->cfg.constrained_intra_pred, n,
-                         slices, out, cap, where);
+                         slices, out, cap, where, c->cabac_split);
+}
+
+// One slice on many waves (include/jmhip_cabac_split.h): a setting of the context, read by the three callers of the writer
+int jmh_cabac_set_split(jmh_ctx *c, int chunk_bins) {
+    if (!c) return JMH_E_INVALID_ARG;
+    if (chunk_bins != 0 && (chunk_bins < 16 || chunk_bins > 65536)) return JMH_E_INVALID_ARG;
+    if (!c->cfg.symbol_mode) return JMH_E_UNSUPPORTED_CFG;
+    c->cabac_split = chunk_bins;
+    return JMH_OK;
+}
+int jmh_cabac_get_split(const jmh_ctx *c) { return c ? c->cabac_split : JMH_E_INVALID_ARG; }
+int jmh_cabac_split_stats(const jmh_ctx *c, jmh_cabac_split_info *out) {
+    if (!c || !out) return JMH_E_INVALID_ARG;
+    jmh_cabac_split_last(c->cabac, out);
+    return JMH_OK;
 }
 
 }  // extern "C"

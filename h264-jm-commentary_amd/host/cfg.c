@@ -68,6 +68,7 @@ static const map_entry Map[] = {
     {"WriterThreads", 0, OFF(writer_threads), 0, 64},
     {"DeviceCAVLC", 0, OFF(device_cavlc), 0, 1},
     {"DeviceCABAC", 0, OFF(device_cabac), 0, 1},
+    {"DeviceCABACSplit", 0, OFF(device_cabac_split), 0, 65536},
     {"DeviceWriterAsync", 0, OFF(device_writer_async), 0, 1},
     {"JMVersion", 0, OFF(jm_version), 8, 99},
     {"QOffsetIntra", 0, OFF(qoff_intra), -1, JMH_QOFFSET_MAX},
@@ -186,6 +187,8 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->rdopt && inp->jm_call_surface) { snprintf(err, errlen, "JMCallSurface=1 checks the RDO-off decision (RDOptimization=0)"); return -1; }
     if (inp->device_cavlc && inp->symbol_mode) { snprintf(err, errlen, "DeviceCAVLC=1 writes CAVLC slice data (SymbolMode=0); with SymbolMode=1 the device writer is DeviceCABAC=1"); return -1; }
     if (inp->device_cabac && !inp->symbol_mode) { snprintf(err, errlen, "DeviceCABAC=1 writes CABAC slice data (SymbolMode=1); with SymbolMode=0 the device writer is DeviceCAVLC=1"); return -1; }
+    if (inp->device_cabac_split && !inp->device_cabac) { snprintf(err, errlen, "DeviceCABACSplit=%d cuts the slices of the device CABAC writer into chunks: it needs DeviceCABAC=1", inp->device_cabac_split); return -1; }
+    if (inp->device_cabac_split && inp->device_cabac_split < 16) { snprintf(err, errlen, "DeviceCABACSplit=%d: with DeviceCABAC=1 a chunk holds 16..65536 bins (0: one wave per slice)", inp->device_cabac_split); return -1; }
     if (inp->device_cabac && inp->jm_call_surface) { snprintf(err, errlen, "DeviceCABAC=1 replaces the write_one_macroblock loop that JMCallSurface=1 runs (JMCallSurface=0)"); return -1; }
     if (inp->device_cavlc && inp->jm_call_surface) { snprintf(err, errlen, "DeviceCAVLC=1 replaces the write_one_macroblock loop that JMCallSurface=1 runs (JMCallSurface=0)"); return -1; }
     if (inp->device_writer_async && !inp->device_cavlc && !inp->device_cabac) { snprintf(err, errlen, "DeviceWriterAsync=1 queues the device slice writer behind each picture: it needs DeviceCAVLC=1 (SymbolMode=0) or DeviceCABAC=1 (SymbolMode=1)"); return -1; }

@@ -142,6 +142,8 @@ static jm_cavlc_slices_fn device_cavlc_fn;
 void jm_set_device_cavlc(jm_cavlc_slices_fn fn) { device_cavlc_fn = fn; }
 static jm_cabac_slices_fn device_cabac_fn;
 void jm_set_device_cabac(jm_cabac_slices_fn fn) { device_cabac_fn = fn; }
+static jm_cabac_split_fn device_cabac_split_fn;
+void jm_set_device_cabac_split(jm_cabac_split_fn fn) { device_cabac_split_fn = fn; }
 /* DeviceWriterAsync 1: the same writers queued behind each pipelined picture (jmh_frame_push_coded /
  * jmh_frame_pop_coded).  The headers are written when the picture is pushed (device_slice_headers:
  * frame_num, slice type, QP and first_mb are known then) and kept with the picture; its pop brings
@@ -381,11 +383,20 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fprintf(stderr, "DeviceCAVLC=1 needs the device backend (backend '%s' writes its slices on the host: DeviceCAVLC=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
     }
+    if (inp->device_cabac_split && !device_cabac_split_fn) {
+        fprintf(stderr, "DeviceCABACSplit=%d with DeviceCABAC=1 needs the device backend (backend '%s' writes its slices on the host: DeviceCABAC=0)\n",
+                inp->device_cabac_split, be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     if (inp->device_cabac && !device_cabac_fn) {
         fprintf(stderr, "DeviceCABAC=1 needs the device backend (backend '%s' writes its slices on the host: DeviceCABAC=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
     }
     const int device_writer = inp->device_cavlc || inp->device_cabac;
+    if (inp->device_cabac_split) {               /* once, before the first picture: every writer call and coded picture follows it */
+        const int r = device_cabac_split_fn(be->ctx, inp->device_cabac_split);
+        if (r) { fprintf(stderr, "DeviceCABACSplit=%d: the backend refused it (%d)\n", inp->device_cabac_split, r); return r; }
+    }
     if (inp->device_writer_async && !(device_coded_push_fn && device_coded_pop_fn)) {
         fprintf(stderr, "DeviceWriterAsync=1 needs the device backend (backend '%s' has no coded push / pop: DeviceWriterAsync=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
@@ -506,7 +517,10 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         if (pipelined) fprintf(log, " (%d pictures in flight%s)\n", depth, nwr ? ", parallel slice writing" : "");
         if (nwr) fprintf(log, " (%d slice-writer threads)\n", nwr);
         if (inp->device_cavlc) fprintf(log, " (CAVLC slice data written on the device)\n");
-        if (inp->device_cabac) fprintf(log, " (CABAC slice data written on the device: no writer threads, no per-macroblock rate check)\n");
+        if (inp->device_cabac && inp->device_cabac_split)
+            fprintf(log, " (CABAC slice data written on the device, every slice in chunks of %d bins: no writer threads, no per-macroblock rate check)\n",
+                    inp->device_cabac_split);
+        else if (inp->device_cabac) fprintf(log, " (CABAC slice data written on the device: no writer threads, no per-macroblock rate check)\n");
         if (async) fprintf(log, " (the slice writer is queued behind each picture: its pop returns the slice bytes and the SSDs)\n");
         fprintf(log, " Frame  Bit/pic  QP   SnrY    SnrU    SnrV    Time(ms) MET(ms) Frm/Fld  I D\n");
     }

@@ -77,6 +77,9 @@ typedef struct jm_input {
                                   and the NAL packaging.  SymbolMode 0, device backend only        */
     int  device_cabac;         /* (this build) DeviceCABAC 1: the same for CABAC slice data (jmh_cabac
                                   _write_slices).  SymbolMode 1, device backend only               */
+    int  device_cabac_split;   /* (this build) DeviceCABACSplit N: with DeviceCABAC 1 every slice is cut into
+                                  chunks of N bins (16..65536) that are coded at once (jmh_cabac_set_split);
+                                  0: one wave per slice.  The stream is the same                      */
     int  device_writer_async;  /* (this build) DeviceWriterAsync 1: with DeviceCAVLC / DeviceCABAC 1 the slice
                                   writer is queued behind each pipelined picture (jmh_frame_push_coded /
                                   jmh_frame_pop_coded); the pop returns the slice bytes and the SSDs, no
@@ -237,6 +240,9 @@ void jm_set_device_cavlc(jm_cavlc_slices_fn fn);
 typedef int (*jm_cabac_slices_fn)(void *ctx, int n, const jmh_cabac_slice_desc *slices, uint8_t *out, size_t cap,
                                   jmh_cabac_slice_bytes *where);
 void jm_set_device_cabac(jm_cabac_slices_fn fn);
+/* DeviceCABACSplit N: set once on the backend's context before the first picture (jmh_cabac_set_split) */
+typedef int (*jm_cabac_split_fn)(void *ctx, int chunk_bins);
+void jm_set_device_cabac_split(jm_cabac_split_fn fn);
 /* DeviceWriterAsync 1: the backend's coded push / pop (jmh_frame_push_coded / jmh_frame_pop_coded,
    include/jmhip_coded.h); unset on a backend without them, where the key is rejected */
 typedef int (*jm_coded_push_fn)(void *ctx, const jm_pic *cur, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,

@@ -49,6 +49,7 @@ static int gpu_cavlc_slices(void *ctx, int n, const jmh_slice_desc *d, uint8_t *
 static int gpu_cabac_slices(void *ctx, int n, const jmh_cabac_slice_desc *d, uint8_t *out, size_t cap, jmh_cabac_slice_bytes *where) {
     return jmh_cabac_write_slices((jmh_ctx *)ctx, n, d, out, cap, where);
 }
+static int gpu_cabac_split(void *ctx, int chunk_bins) { return jmh_cabac_set_split((jmh_ctx *)ctx, chunk_bins); }
 static int gpu_push_coded(void *ctx, const jm_pic *cur, const jmh_frame_params *fp, int n, const jmh_coded_slice *sl, int cw, int ch) {
     if (cur->bd > 8) return jmh_frame_push_coded_u16((jmh_ctx *)ctx, cur->Y, cur->U, cur->V, cur->w, cur->w / 2, fp, n, sl, cw, ch);
     return jmh_frame_push_coded((jmh_ctx *)ctx, cur->y, cur->u, cur->v, cur->w, cur->w / 2, fp, n, sl, cw, ch);
@@ -75,6 +76,7 @@ int main(int argc, char **argv) {
                      gpu_search_pictures, gpu_block_search, gpu_tq4x4};
     jm_set_device_cavlc(gpu_cavlc_slices);
     jm_set_device_cabac(gpu_cabac_slices);
+    jm_set_device_cabac_split(gpu_cabac_split);
     jm_set_device_coded(gpu_push_coded, gpu_pop_coded);
     if (getenv("JMH_HOST_DEBLOCK")) be.read_deblocked = NULL, be.reference_deblocked = NULL;
     jm_stats st;

@@ -226,6 +226,20 @@ _SIGS_CODED = {
 EXPORTED_CODED = tuple(_SIGS_CODED)
 
 
+# ---- one CABAC slice on many waves (include/jmhip_cabac_split.h; additive to ABI 14) ----
+class JmhCabacSplitInfo(ctypes.Structure):
+    _fields_ = [("chunk_bins", ctypes.c_int32), ("reserved", ctypes.c_int32), ("chunks", ctypes.c_int64),
+                ("longest_slice_chunks", ctypes.c_int64), ("scratch_bytes", ctypes.c_int64)]
+
+
+_SIGS_CABAC_SPLIT = {
+    "jmh_cabac_set_split": (_I, [_P, _I]),
+    "jmh_cabac_get_split": (_I, [_P]),
+    "jmh_cabac_split_stats": (_I, [_P, _P]),
+}
+EXPORTED_CABAC_SPLIT = tuple(_SIGS_CABAC_SPLIT)
+
+
 def coded_slice_descs(nmb, slice_type, qp, mbs_per_slice=0, lead=()):
     """The descriptors of a coded picture (a JmhCodedSlice array), from the two writers' helpers:
     the raster runs and lead bits of slice_descs, the slice QPs of cabac_slice_descs."""
@@ -271,7 +285,8 @@ def load(path=LIB_PATH):
     if not os.path.exists(path):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()):
+    for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()) + \
+            list(_SIGS_CABAC_SPLIT.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -570,6 +585,20 @@ class Encoder:
             raise JmhError(f"cabac_results: {res.size} results for {self.mbw * self.mbh} macroblocks")
         return self._cabac(lambda *a: self.lib.jmh_cabac_write_results(self.ctx, _ptr(res), *a), "jmh_cabac_write_results", descs, cap,
                            with_where)
+
+    def cabac_split(self, chunk_bins):
+        """jmh_cabac_set_split: the CABAC writer (cabac_slices, cabac_results, coded pictures pushed from
+        now on) cuts every slice into chunks of chunk_bins bins (16..65536) and codes all of them at
+        once; 0 (the state of a new encoder): one wave per slice.  The bytes are the same."""
+        _check(self.lib.jmh_cabac_set_split(self.ctx, int(chunk_bins)), "jmh_cabac_set_split")
+
+    def cabac_split_info(self):
+        """jmh_cabac_split_stats of the last cabac_slices / cabac_results call: a dict of chunk_bins (0:
+        it ran unsplit), chunks, longest_slice_chunks, scratch_bytes; and the current setting."""
+        info = JmhCabacSplitInfo()
+        _check(self.lib.jmh_cabac_split_stats(self.ctx, ctypes.byref(info)), "jmh_cabac_split_stats")
+        return dict(chunk_bins=info.chunk_bins, chunks=info.chunks, longest_slice_chunks=info.longest_slice_chunks,
+                    scratch_bytes=info.scratch_bytes, setting=self.lib.jmh_cabac_get_split(self.ctx))
 
     # ---- unit seams ----
     def sad_table(self, mb_xy, centres):

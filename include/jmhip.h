@@ -379,4 +379,5 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #include "jmhip_cavlc.h"
 #include "jmhip_cabac.h"
 #include "jmhip_coded.h"
+#include "jmhip_cabac_split.h"
 #endif /* JMHIP_H */
