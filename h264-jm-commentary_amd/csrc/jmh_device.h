@@ -236,6 +236,16 @@ struct FlowArgs {
 };
 #define FLOW_ITEM(e, x, y) (((uint32_t)(e) << 24) | ((uint32_t)(y) << 12) | (uint32_t)(x))
 
+// k_ingest (jmh_ingest.hip): a device picture of w x h luma samples into the packed W x H source
+struct IngestArgs {
+    const uint8_t *plane[3];             // device planes of the caller (jmhip_input.h), [2] unused when UV is interleaved
+    int64_t stride[3];                   // bytes per row
+    uint8_t *dst;                        // Y, U, V of the coded size, samples of 1 or 2 bytes
+    int w, h, W, H;
+    uint32_t maxv;
+    unsigned long long *clamped;         // I010: samples above maxv are added here
+};
+
 // XCD-aware block order.  Workgroups are dispatched round-robin over the 8 XCDs (hardware block b
 // runs on XCD b % 8), each with its own L2.  A launch of n logical blocks uses 8 * ceil(n / 8)
 // hardware blocks and gives every XCD one contiguous run of the logical list, whose consecutive

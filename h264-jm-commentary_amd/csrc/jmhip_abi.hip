@@ -23,6 +23,7 @@
 #include "jmh_cavlc.h"
 #include "jmh_cabac.h"
 #include "jmh_cabac_rate.h"
+#include "jmh_ingest.h"
 
 // Coded pictures: bytes of output per macroblock that a picture's writer is queued with, unless
 // JMH_CODED_CAP says otherwise.  192 B per MB is about four times the densest picture recorded
@@ -115,6 +116,9 @@ struct PicBuf {
     jmh_coded_slice *cd_sl;              // pinned (inside cd_h): the caller's descriptors, for the synchronous fallback
     uint8_t *cd_out;                     // device: the picture's output region
     size_t cd_cap;                       //   its bytes
+    // device pictures (jmhip_input.h)
+    int dev_fmt;                         // the occupant was pushed from device memory: its format + 1, else 0
+    hipEvent_t ev_in;                    //   the caller's stream at the push (created on first use)
 };
 
 // offsets into PicBuf::cd_h / cd_d (each a multiple of 8)
@@ -217,6 +221,14 @@ struct jmh_ctx {
     size_t coded_cap = 0;                // coded pictures: bytes of output per macroblock queued with a picture
     std::vector<void *> coded_retired;   //   outgrown output regions: freed with the context
     uint8_t *h_coded_pic = nullptr;      //   pinned: jmh_read_recon / jmh_read_deblocked of a coded picture
+    // device pictures: the I010 clamp counts, a word per ring entry and one for the unit seam (on the
+    // first I010 picture), the count of the picture last popped, the last device push
+    unsigned long long *d_clamp = nullptr, *h_clamp = nullptr;
+    uint64_t last_clamped = 0;
+    int last_dev_entry = -1;
+    uint8_t *up_h = nullptr;             // jmh_device_upload on a stream: its pinned buffer,
+    size_t up_cap = 0;
+    hipEvent_t ev_up = nullptr;          //   the last copy out of it
 };
 
 #define HCHK(x)                                                                  \
@@ -258,7 +270,7 @@ static void free_entry(PicBuf &b) {
     for (void *p : dev_bufs) if (p) (void)hipFree(p);
     void *host_bufs[] = {b.h_res, b.h_src, b.h_rec, b.h_dbk, b.h_rp, b.cd_h};
     for (void *p : host_bufs) if (p) (void)hipHostFree(p);
-    hipEvent_t evs[] = {b.ev_src, b.ev_t0, b.ev_done, b.ev_fin, b.ev_rp};
+    hipEvent_t evs[] = {b.ev_src, b.ev_t0, b.ev_done, b.ev_fin, b.ev_rp, b.ev_in};
     for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
 }
 
@@ -287,14 +299,15 @@ static int alloc_entry(jmh_ctx *c, PicBuf &b) {
     return JMH_OK;
 }
 
-// pinned readback / staging, on first use: all four buffers or none (a partial allocation is
+// pinned readback / staging, on first use: all four buffers (with_src false, a device picture: the
+// three of the readback) or none (a partial allocation is
 // released, so a later call retries instead of seeing a half-initialised entry)
-static int alloc_host(jmh_ctx *c, PicBuf &b) {
-    if (b.h_res && b.h_src && b.h_rec && b.h_dbk) return JMH_OK;
+static int alloc_host(jmh_ctx *c, PicBuf &b, bool with_src) {
+    if (b.h_res && (b.h_src || !with_src) && b.h_rec && b.h_dbk) return JMH_OK;
     void **bufs[4] = {(void **)&b.h_res, (void **)&b.h_src, (void **)&b.h_rec, (void **)&b.h_dbk};
     const size_t sizes[4] = {c->nmb * sizeof(jmh_mb_result), c->fsize, c->fsize, c->fsize};
     for (int i = 0; i < 4; i++)
-        if (!*bufs[i] && hipHostMalloc(bufs[i], sizes[i], hipHostMallocDefault) != hipSuccess) {
+        if (!*bufs[i] && (i != 1 || with_src) && hipHostMalloc(bufs[i], sizes[i], hipHostMallocDefault) != hipSuccess) {
             *bufs[i] = nullptr;
             for (int k = 0; k < 4; k++)
                 if (*bufs[k]) { (void)hipHostFree(*bufs[k]); *bufs[k] = nullptr; }
@@ -381,6 +394,10 @@ void jmh_destroy(jmh_ctx *c) {
     for (PicBuf &b : c->ring) free_entry(b);
     for (void *p : c->coded_retired) (void)hipFree(p);
     if (c->h_coded_pic) (void)hipHostFree(c->h_coded_pic);
+    if (c->d_clamp) (void)hipFree(c->d_clamp);
+    if (c->h_clamp) (void)hipHostFree(c->h_clamp);
+    if (c->up_h) (void)hipHostFree(c->up_h);
+    if (c->ev_up) (void)hipEventDestroy(c->ev_up);
     void *dev_bufs[] = {c->d_ref, c->d_qpel, c->d_slots, c->d_prof, c->d_bprof, c->spic[0].cur, c->spic[0].ref, c->d_ordtab, c->spic[1].cur,
                         c->spic[1].ref, c->d_sched, c->d_soff, c->d_rscr, c->d_ffs, c->d_seg[0], c->d_seg[1], c->d_flags, c->d_head,
                         c->d_fprof};
@@ -1142,12 +1159,44 @@ static int alloc_coded(jmh_ctx *c, PicBuf &b) {
     return JMH_OK;
 }
 
-static int frame_push_any(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const jmh_frame_params *fp, bool wide,
-                          const CodedPush *cp = nullptr) {
-    if (!c || !y || !u || !v || !fp || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
-    int r = check_params(c, fp);
-    if (r) return r;
-    if ((r = check_pic(c, wide))) return r;
+// the source of a pushed picture: host planes (strides in samples) or a device picture
+struct PushSrc { const void *y, *u, *v; int sy, sc; bool wide; const jmh_device_picture *dev; };
+
+static int check_device_pic(const jmh_ctx *c, const jmh_device_picture *p) {
+    if (!p || jmi_check(p->format, p->width, p->height, c->W, c->H, p->plane, p->stride)) return JMH_E_INVALID_ARG;
+    return JMH_OK;
+}
+
+// k_ingest of p into dst on the context's stream, behind the work queued on the caller's stream so
+// far (ev: that stream's event); slot: the clamp word of an I010 picture
+static int ingest_queue(jmh_ctx *c, const jmh_device_picture *p, uint8_t *dst, int slot, hipEvent_t ev) {
+    if (p->stream) {
+        HCHK(hipEventRecord(ev, (hipStream_t)p->stream));
+        HCHK(hipStreamWaitEvent(c->st, ev, 0));
+    }
+    IngestArgs a;
+    for (int i = 0; i < 3; i++) { a.plane[i] = (const uint8_t *)p->plane[i]; a.stride[i] = p->stride[i]; }
+    a.dst = dst; a.w = p->width; a.h = p->height; a.W = c->W; a.H = c->H; a.maxv = (uint32_t)c->maxv; a.clamped = nullptr;
+    const bool counts = p->format == JMH_PIX_I010;
+    if (counts) {
+        const size_t nb = (size_t)(c->nring + 1) * sizeof(unsigned long long);
+        if (!c->d_clamp && hipMalloc((void **)&c->d_clamp, nb) != hipSuccess) { c->d_clamp = nullptr; return JMH_E_OOM; }
+        if (!c->h_clamp && hipHostMalloc((void **)&c->h_clamp, nb, hipHostMallocDefault) != hipSuccess) { c->h_clamp = nullptr; return JMH_E_OOM; }
+        a.clamped = c->d_clamp + slot;
+        HCHK(hipMemsetAsync(a.clamped, 0, sizeof(unsigned long long), c->st));
+    }
+    HCHK(jmh_launch_ingest(p->format, a, c->st));
+    if (counts) HCHK(hipMemcpyAsync(c->h_clamp + slot, a.clamped, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
+    return JMH_OK;
+}
+
+static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *fp, const CodedPush *cp = nullptr) {
+    if (!c || !fp) return JMH_E_INVALID_ARG;
+    int r;
+    if (s.dev) { if ((r = check_device_pic(c, s.dev))) return r; }
+    else if (!s.y || !s.u || !s.v || s.sy < c->W || s.sc < c->Wc) return JMH_E_INVALID_ARG;
+    if ((r = check_params(c, fp))) return r;
+    if ((r = s.dev ? (jmi_depth_ok(s.dev->format, c->bd) ? JMH_OK : JMH_E_UNSUPPORTED_CFG) : check_pic(c, s.wide))) return r;
     std::vector<uint8_t> descs;
     if (cp) {   // before anything is claimed or queued
         if (cp->cw <= 0 || cp->ch <= 0 || cp->cw > c->W || cp->ch > c->H) return JMH_E_INVALID_ARG;
@@ -1159,18 +1208,31 @@ static int frame_push_any(jmh_ctx *c, const void *y, const void *u, const void *
     int e;
     if ((r = claim_entry(c, &e))) return r;
     PicBuf &b = c->ring[e];
-    if (cp) {   // no readback: the source staging only
-        if (!b.h_src && hipHostMalloc((void **)&b.h_src, c->fsize, hipHostMallocDefault) != hipSuccess) { b.h_src = nullptr; return JMH_E_OOM; }
+    if (cp) {   // no readback: the source staging only (a device picture: none)
+        if (!s.dev && !b.h_src && hipHostMalloc((void **)&b.h_src, c->fsize, hipHostMallocDefault) != hipSuccess) { b.h_src = nullptr; return JMH_E_OOM; }
         if ((r = alloc_coded(c, b))) return r;
-    } else if ((r = alloc_host(c, b))) return r;
-    HCHK(hipEventSynchronize(b.ev_src));   // the previous H2D out of this staging buffer
-    // an out-of-range sample rejects the picture before its own copy or ticks are queued: the
-    // claimed entry stays free (nothing refers to it).  Not side-effect free: claiming the entry
-    // may already have issued ticks of earlier pictures (legal progress of their wavefronts)
-    if (!pack_planes(b.h_src, c->W, c->H, y, u, v, sy, sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
-    HCHK(hipEventRecord(b.ev_t0, c->st));
-    HCHK(hipMemcpyAsync(b.src, b.h_src, c->fsize, hipMemcpyHostToDevice, c->st));
-    HCHK(hipEventRecord(b.ev_src, c->st));
+    } else if ((r = alloc_host(c, b, !s.dev))) return r;
+    if (s.dev) {
+        // the device picture packed and padded where a host picture is uploaded: between ev_t0 and
+        // ev_src on the context's stream.  The caller's stream then waits for ev_src, so what it
+        // is given after this call may overwrite the planes
+        if (s.dev->stream && !b.ev_in && hipEventCreateWithFlags(&b.ev_in, hipEventDisableTiming) != hipSuccess) { b.ev_in = nullptr; return JMH_E_HIP; }
+        HCHK(hipEventRecord(b.ev_t0, c->st));
+        if ((r = ingest_queue(c, s.dev, b.src, e, b.ev_in))) return r;
+        HCHK(hipEventRecord(b.ev_src, c->st));
+        if (s.dev->stream) HCHK(hipStreamWaitEvent((hipStream_t)s.dev->stream, b.ev_src, 0));
+        c->last_dev_entry = e;
+    } else {
+        HCHK(hipEventSynchronize(b.ev_src));   // the previous H2D out of this staging buffer
+        // an out-of-range sample rejects the picture before its own copy or ticks are queued: the
+        // claimed entry stays free (nothing refers to it).  Not side-effect free: claiming the entry
+        // may already have issued ticks of earlier pictures (legal progress of their wavefronts)
+        if (!pack_planes(b.h_src, c->W, c->H, s.y, s.u, s.v, s.sy, s.sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
+        HCHK(hipEventRecord(b.ev_t0, c->st));
+        HCHK(hipMemcpyAsync(b.src, b.h_src, c->fsize, hipMemcpyHostToDevice, c->st));
+        HCHK(hipEventRecord(b.ev_src, c->st));
+    }
+    b.dev_fmt = s.dev ? s.dev->format + 1 : 0;
     b.coded = cp != nullptr;
     if (cp) {
         const CodedLayout L(c->nmb);
@@ -1183,21 +1245,94 @@ static int frame_push_any(jmh_ctx *c, const void *y, const void *u, const void *
 }
 extern "C" {
 int jmh_frame_push(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp) {
-    return frame_push_any(c, y, u, v, sy, sc, fp, false);
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, nullptr}, fp);
 }
 int jmh_frame_push_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp) {
-    return frame_push_any(c, y, u, v, sy, sc, fp, true);
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, nullptr}, fp);
 }
 
 int jmh_frame_push_coded(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp, int n,
                          const jmh_coded_slice *slices, int crop_w, int crop_h) {
     const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, y, u, v, sy, sc, fp, false, &cp);
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, nullptr}, fp, &cp);
 }
 int jmh_frame_push_coded_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp,
                              int n, const jmh_coded_slice *slices, int crop_w, int crop_h) {
     const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, y, u, v, sy, sc, fp, true, &cp);
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, nullptr}, fp, &cp);
+}
+
+// ---- pictures that are already on the device (include/jmhip_input.h) ----
+int jmh_frame_push_device(jmh_ctx *c, const jmh_device_picture *pic, const jmh_frame_params *fp) {
+    if (!pic) return JMH_E_INVALID_ARG;
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, pic}, fp);
+}
+int jmh_frame_push_coded_device(jmh_ctx *c, const jmh_device_picture *pic, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
+                                int crop_w, int crop_h) {
+    if (!pic) return JMH_E_INVALID_ARG;
+    const CodedPush cp = {n, slices, crop_w, crop_h};
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, pic}, fp, &cp);
+}
+int jmh_device_input_wait(jmh_ctx *c) {
+    if (!c) return JMH_E_INVALID_ARG;
+    if (c->last_dev_entry < 0) return JMH_OK;
+    HCHK(hipSetDevice(c->dev));
+    HCHK(hipEventSynchronize(c->ring[c->last_dev_entry].ev_src));   // (a later occupant's event has passed the picture's too)
+    return JMH_OK;
+}
+int jmh_device_input_clamped(const jmh_ctx *c, uint64_t *n) {
+    if (!c || !n) return JMH_E_INVALID_ARG;
+    *n = c->last_clamped;
+    return JMH_OK;
+}
+int jmh_device_malloc(jmh_ctx *c, size_t n, void **p) {
+    if (!c || !p || !n) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    if (hipMalloc(p, n) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return JMH_E_OOM; }
+    return JMH_OK;
+}
+int jmh_device_free(jmh_ctx *c, void *p) {
+    if (!c) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    if (p) HCHK(hipFree(p));
+    return JMH_OK;
+}
+int jmh_device_upload(jmh_ctx *c, void *dst, const void *src, size_t n, void *stream) {
+    if (!c || !dst || !src) return JMH_E_INVALID_ARG;
+    if (!n) return JMH_OK;
+    HCHK(hipSetDevice(c->dev));
+    if (!stream) {
+        HCHK(hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
+        return JMH_OK;
+    }
+    // through the context's pinned buffer: src is free on return, the copy itself runs on the stream
+    if (!c->ev_up) { if (hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming) != hipSuccess) { c->ev_up = nullptr; return JMH_E_HIP; } }
+    else HCHK(hipEventSynchronize(c->ev_up));
+    if (n > c->up_cap) {
+        if (c->up_h) (void)hipHostFree(c->up_h);
+        c->up_h = nullptr; c->up_cap = 0;
+        if (hipHostMalloc((void **)&c->up_h, n, hipHostMallocDefault) != hipSuccess) { c->up_h = nullptr; return JMH_E_OOM; }
+        c->up_cap = n;
+    }
+    memcpy(c->up_h, src, n);
+    HCHK(hipMemcpyAsync(dst, c->up_h, n, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HCHK(hipEventRecord(c->ev_up, (hipStream_t)stream));
+    return JMH_OK;
+}
+int jmh_device_stream_create(jmh_ctx *c, void **stream) {
+    if (!c || !stream) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    hipStream_t st = nullptr;
+    HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    *stream = st;
+    return JMH_OK;
+}
+int jmh_device_stream_destroy(jmh_ctx *c, void *stream) {
+    if (!c || !stream) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    HCHK(hipStreamSynchronize((hipStream_t)stream));
+    HCHK(hipStreamDestroy((hipStream_t)stream));
+    return JMH_OK;
 }
 
 }  // extern "C"
@@ -1221,6 +1356,7 @@ static void pop_done(jmh_ctx *c, int e) {
     c->popq.pop_front();
     c->ring[e].unpopped = 0;
     c->cur_entry = e;
+    c->last_clamped = c->ring[e].dev_fmt == JMH_PIX_I010 + 1 ? c->h_clamp[e] : 0;
     float ms = 0;
     if (hipEventElapsedTime(&ms, c->ring[e].ev_t0, c->ring[e].ev_done) == hipSuccess) c->timing.total_ms = ms;
 }
@@ -1384,6 +1520,32 @@ static int load_frame_any(jmh_ctx *c, int slot, const void *y, const void *u, co
     if (!pack_planes(c->h_stage_ref, c->W, c->H, y, u, v, sy, sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
     HCHK(hipMemcpyAsync(c->d_slots + (size_t)slot * c->fsize, c->h_stage_ref, c->fsize, hipMemcpyHostToDevice, c->st));
     HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+
+// the unit seam of k_ingest: the kernel into a scratch picture, the packed planes to the host
+extern "C" int jmh_ingest_picture(jmh_ctx *c, const jmh_device_picture *pic, void *y, void *u, void *v, int sy, int sc) {
+    if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
+    int r = check_device_pic(c, pic);
+    if (r) return r;
+    if (!jmi_depth_ok(pic->format, c->bd)) return JMH_E_UNSUPPORTED_CFG;
+    HCHK(hipSetDevice(c->dev));
+    DevTemps t;
+    uint8_t *d = nullptr;
+    if (t.alloc(&d, c->fsize) != hipSuccess) return JMH_E_OOM;
+    hipEvent_t ev = nullptr;
+    if (pic->stream) HCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    r = ingest_queue(c, pic, d, c->nring, ev);
+    if (!r && pic->stream && (hipEventRecord(ev, c->st) != hipSuccess || hipStreamWaitEvent((hipStream_t)pic->stream, ev, 0) != hipSuccess))
+        r = JMH_E_HIP;
+    const hipError_t se = hipStreamSynchronize(c->st);
+    if (ev) (void)hipEventDestroy(ev);
+    if (r) return r;
+    HCHK(se);
+    std::vector<uint8_t> h(c->fsize);
+    HCHK(hipMemcpy(h.data(), d, c->fsize, hipMemcpyDeviceToHost));
+    unpack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps);
+    c->last_clamped = pic->format == JMH_PIX_I010 ? c->h_clamp[c->nring] : 0;
     return JMH_OK;
 }
 

@@ -397,6 +397,11 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         const int r = device_cabac_split_fn(be->ctx, inp->device_cabac_split);
         if (r) { fprintf(stderr, "DeviceCABACSplit=%d: the backend refused it (%d)\n", inp->device_cabac_split, r); return r; }
     }
+    const jm_device_push_fn device_input_fn = inp->device_input ? jm_device_input() : NULL;
+    if (inp->device_input && !device_input_fn) {
+        fprintf(stderr, "DeviceInput=1 needs the device backend (backend '%s' has no device input: DeviceInput=0)\n", be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     if (inp->device_writer_async && !(device_coded_push_fn && device_coded_pop_fn)) {
         fprintf(stderr, "DeviceWriterAsync=1 needs the device backend (backend '%s' has no coded push / pop: DeviceWriterAsync=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
@@ -437,8 +442,8 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     const int pipelined = dev_dbk && be->push && be->pop && be->depth > 1;
     const int depth = pipelined ? be->depth : 1;
     const int async = inp->device_writer_async;
-    if (async && !pipelined) {
-        fprintf(stderr, "DeviceWriterAsync=1 needs the pipelined path (device deblocking, more than one picture in flight)\n");
+    if ((async || device_input_fn) && !pipelined) {
+        fprintf(stderr, "%s=1 needs the pipelined path (device deblocking, more than one picture in flight)\n", async ? "DeviceWriterAsync" : "DeviceInput");
         if (fin) fclose(fin);
         fclose(fout);
         if (frec) fclose(frec);
@@ -463,6 +468,10 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fclose(fout);
         if (frec) fclose(frec);
         return JMH_E_OOM;
+    }
+    if (device_input_fn) {   /* the readers write the display size only: what lies outside is the device's to pad, never this */
+        jm_source_padding(0);
+        for (int k = 0; k < plen; k++) memset(bd > 8 ? (void *)pend[k].cur.Y : (void *)pend[k].cur.y, 0x5A, (size_t)W * H * 3 / 2 * (bd > 8 ? 2 : 1));
     }
     int nmb = s.mbw * s.mbh;
     const jmh_mb_result **res = (const jmh_mb_result **)malloc(sizeof(*res) * nmb);
@@ -521,6 +530,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             fprintf(log, " (CABAC slice data written on the device, every slice in chunks of %d bins: no writer threads, no per-macroblock rate check)\n",
                     inp->device_cabac_split);
         else if (inp->device_cabac) fprintf(log, " (CABAC slice data written on the device: no writer threads, no per-macroblock rate check)\n");
+        if (device_input_fn) fprintf(log, " (the source is uploaded as read and pushed from device memory: the device pads it to the coded size)\n");
         if (async) fprintf(log, " (the slice writer is queued behind each picture: its pop returns the slice bytes and the SSDs)\n");
         fprintf(log, " Frame  Bit/pic  QP   SnrY    SnrU    SnrV    Time(ms) MET(ms) Frm/Fld  I D\n");
     }
@@ -695,9 +705,11 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             jm_slice sl;
             PEND_SLICE(p, sl);
             device_slice_headers(d, &s, &sl);
-            r = device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
+            r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
+                                : device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
         } else
-        if (!r) r = pipelined ? be->push(be->ctx, &p->cur, fp) : be->encode_frame(be->ctx, &p->cur, fp);
+        if (!r) r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, 0, NULL, 0, 0)
+                  : pipelined ? be->push(be->ctx, &p->cur, fp) : be->encode_frame(be->ctx, &p->cur, fp);
         double met = now_ms() - t0;
         if (r) { fprintf(stderr, "hot path backend '%s' failed: status %d\n", be->name, r); st_ret = r; break; }
         st->me_tq_ms += met;
@@ -726,6 +738,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     #undef FLUSH_JOB
     st->total_ms = now_ms() - t_start;
 cleanup:
+    jm_source_padding(1);
     /* one teardown for every exit: stop and join the writer threads that started, free what
        was allocated (also after a partial setup) */
     if (nstarted) {

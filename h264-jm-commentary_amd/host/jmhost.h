@@ -84,6 +84,10 @@ typedef struct jm_input {
                                   writer is queued behind each pipelined picture (jmh_frame_push_coded /
                                   jmh_frame_pop_coded); the pop returns the slice bytes and the SSDs, no
                                   results or pictures cross to the host (ReconFile: the picture on demand) */
+    int  device_input;         /* (this build) DeviceInput 1: the picture as read (display size, unpadded) is
+                                  uploaded raw and pushed from device memory (jmh_frame_push_device /
+                                  jmh_frame_push_coded_device); the device pads it to the coded size.
+                                  Pipelined device backend only; the stream is the same              */
     int  verbose;
 } jm_input;
 
@@ -118,6 +122,9 @@ void jm_synth_frame_hbd(uint16_t *y, uint16_t *u, uint16_t *v, int w, int h, int
 int  jm_read_yuv_frame(FILE *f, jm_pic *p, int disp_w, int disp_h, int index);
 int  jm_write_yuv_frame(FILE *f, const jm_pic *p, int disp_w, int disp_h);
 void jm_pad_picture(jm_pic *p, int disp_w, int disp_h);
+/* DeviceInput 1: jm_synth_frame and jm_read_yuv_frame leave the padding to the device (on = 0: the
+   coded picture outside disp_w x disp_h is not written); 1, the default: they pad as described */
+void jm_source_padding(int on);
 
 /* ---- bitstream writer ------------------------------------------------------------------ */
 typedef struct jm_bits {
@@ -249,6 +256,14 @@ typedef int (*jm_coded_push_fn)(void *ctx, const jm_pic *cur, const jmh_frame_pa
                                 int crop_w, int crop_h);
 typedef int (*jm_coded_pop_fn)(void *ctx, uint8_t *out, size_t cap, jmh_coded_bytes *where, jmh_coded_stats *stats);
 void jm_set_device_coded(jm_coded_push_fn push, jm_coded_pop_fn pop);
+/* DeviceInput 1: the backend's push of a picture from device memory (jmh_frame_push_device; with n
+   slices jmh_frame_push_coded_device, include/jmhip_input.h).  cur holds disp_w x disp_h samples at
+   the coded picture's strides, unpadded.  Registered before jm_configure: PatchInp rejects the key
+   on a backend without one */
+typedef int (*jm_device_push_fn)(void *ctx, const jm_pic *cur, int disp_w, int disp_h, const jmh_frame_params *fp, int n,
+                                 const jmh_coded_slice *slices, int crop_w, int crop_h);
+void jm_set_device_input(jm_device_push_fn fn);
+jm_device_push_fn jm_device_input(void);
 /* 10 log10(peak^2 w h / ssd) with psnr_pl's arithmetic (99.0 at ssd 0): the PSNR of a w x h plane of
    bit_depth-bit samples from its summed squared error */
 double jm_psnr_from_ssd(uint64_t ssd, int w, int h, int bit_depth);

@@ -57,11 +57,42 @@ static int gpu_push_coded(void *ctx, const jm_pic *cur, const jmh_frame_params *
 static int gpu_pop_coded(void *ctx, uint8_t *out, size_t cap, jmh_coded_bytes *where, jmh_coded_stats *stats) {
     return jmh_frame_pop_coded((jmh_ctx *)ctx, out, cap, where, stats);
 }
+/* DeviceInput 1: the picture as read (display size, the coded picture's strides, unpadded) uploaded
+   raw into one device buffer and pushed from there.  The upload and the push share a stream of the
+   caller's, so the next picture's upload follows this picture's packing kernel. */
+static struct { void *buf, *stream; size_t bytes; } gpu_in;
+static int gpu_push_device(void *ctx, const jm_pic *cur, int dw, int dh, const jmh_frame_params *fp, int n, const jmh_coded_slice *sl, int cw,
+                           int ch) {
+    const size_t ps = cur->bd > 8 ? 2 : 1, luma = (size_t)cur->w * cur->h * ps, bytes = luma * 3 / 2;
+    int r;
+    if (!gpu_in.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_in.stream))) return r;
+    if (gpu_in.bytes < bytes) {
+        if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_in.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_in.buf))) return r;
+        gpu_in.bytes = bytes;
+    }
+    if ((r = jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, cur->bd > 8 ? (const void *)cur->Y : (const void *)cur->y, bytes, gpu_in.stream))) return r;
+    jmh_device_picture pic;
+    memset(&pic, 0, sizeof(pic));
+    pic.format = cur->bd > 8 ? JMH_PIX_I010 : JMH_PIX_I420;
+    pic.width = dw; pic.height = dh;
+    pic.plane[0] = gpu_in.buf;
+    pic.plane[1] = (const uint8_t *)gpu_in.buf + luma;
+    pic.plane[2] = (const uint8_t *)gpu_in.buf + luma + luma / 4;
+    pic.stride[0] = (int64_t)cur->w * ps; pic.stride[1] = pic.stride[2] = (int64_t)(cur->w / 2) * ps;
+    pic.stream = gpu_in.stream;
+    return n ? jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch) : jmh_frame_push_device((jmh_ctx *)ctx, &pic, fp);
+}
+static void gpu_input_release(void *ctx) {
+    if (gpu_in.stream) (void)jmh_device_stream_destroy((jmh_ctx *)ctx, gpu_in.stream);
+    if (gpu_in.buf) (void)jmh_device_free((jmh_ctx *)ctx, gpu_in.buf);
+    memset(&gpu_in, 0, sizeof(gpu_in));
+}
 
 int main(int argc, char **argv) {
     jm_input inp;
     char err[1024];
     jm_input_defaults(&inp);
+    jm_set_device_input(gpu_push_device);   /* before PatchInp: it rejects DeviceInput on a backend without one */
     if (jm_configure(&inp, argc, argv, err, sizeof(err))) { fprintf(stderr, "%s\n", err); return 1; }
     jmh_config cfg;
     jm_fill_config(&inp, &cfg);
@@ -84,6 +115,7 @@ int main(int argc, char **argv) {
     double mp = (double)inp.width * inp.height * st.frames / 1e6;
     if (!r && st.me_tq_ms > 0)
         printf(" ME+TQ throughput (host-observed, incl. PCIe): %.2f MP/s\n", mp / (st.me_tq_ms / 1e3));
+    gpu_input_release(ctx);
     be.destroy(ctx);
     return r ? 3 : 0;
 }

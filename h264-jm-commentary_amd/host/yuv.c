@@ -51,6 +51,10 @@ void jm_pic_free(jm_pic *p) {
                 memcpy(pl[k] + (size_t)y * cw, pl[k] + (size_t)(cdh - 1) * cw, cw * sizeof(T));          \
         }                                                                                               \
     } while (0)
+static int s_source_padding = 1;
+void jm_source_padding(int on) { s_source_padding = on; }
+/* what the source readers do with a picture they have written */
+static void pad_source(jm_pic *p, int dw, int dh) { if (s_source_padding) jm_pad_picture(p, dw, dh); }
 void jm_pad_picture(jm_pic *p, int dw, int dh) {
     if (p->bd > 8) PAD_PLANES(uint16_t, p->Y, p->U, p->V);
     else PAD_PLANES(uint8_t, p->y, p->u, p->v);
@@ -69,7 +73,7 @@ static int read_hbd(FILE *f, jm_pic *p, int dw, int dh, int index) {
     const int maxv = (1 << p->bd) - 1;
     for (size_t i = 0; i < (size_t)p->w * p->h * 3 / 2; i++)
         if (p->Y[i] > maxv) p->Y[i] = (uint16_t)maxv;     /* samples beyond the bit depth: Clip1 */
-    jm_pad_picture(p, dw, dh);
+    pad_source(p, dw, dh);
     return 0;
 }
 
@@ -89,7 +93,7 @@ int jm_read_yuv_frame(FILE *f, jm_pic *p, int dw, int dh, int index) {
         for (int y = 0; y < dh / 2; y++)
             if (fread(p->v + (size_t)y * (p->w / 2), 1, dw / 2, f) != (size_t)(dw / 2)) return -1;
     }
-    jm_pad_picture(p, dw, dh);
+    pad_source(p, dw, dh);
     return 0;
 }
 
@@ -175,7 +179,7 @@ void jm_synth_frame_hbd(uint16_t *Y, uint16_t *U, uint16_t *V, int w, int h, int
     jm_pic view;
     memset(&view, 0, sizeof(view));
     view.w = w; view.h = h; view.bd = bd; view.Y = Y; view.U = U; view.V = V;
-    jm_pad_picture(&view, dw, dh);
+    pad_source(&view, dw, dh);
 }
 
 static void synth8(jm_pic *p, int dw, int dh, uint64_t seed, int t) {
@@ -220,5 +224,5 @@ static void synth8(jm_pic *p, int dw, int dh, uint64_t seed, int t) {
                 P[(size_t)y * cw + x] = (uint8_t)(v < 16 ? 16 : v > 240 ? 240 : v);
             }
     }
-    jm_pad_picture(p, dw, dh);
+    pad_source(p, dw, dh);
 }

@@ -240,6 +240,106 @@ _SIGS_CABAC_SPLIT = {
 EXPORTED_CABAC_SPLIT = tuple(_SIGS_CABAC_SPLIT)
 
 
+# ---- pictures that are already on the device (include/jmhip_input.h; additive to ABI 14) ----
+JMH_PIX_I420, JMH_PIX_NV12, JMH_PIX_I010, JMH_PIX_P010 = 0, 1, 2, 3
+
+
+class JmhDevicePicture(ctypes.Structure):
+    _fields_ = [("format", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("plane", ctypes.c_void_p * 3), ("stride", ctypes.c_int64 * 3), ("stream", ctypes.c_void_p)]
+
+
+_SIGS_INPUT = {
+    "jmh_frame_push_device": (_I, [_P, _P, ctypes.POINTER(JmhFrameParams)]),
+    "jmh_frame_push_coded_device": (_I, [_P, _P, ctypes.POINTER(JmhFrameParams), _I, _P, _I, _I]),
+    "jmh_ingest_picture": (_I, [_P, _P, _P, _P, _P, _I, _I]),
+    "jmh_device_input_wait": (_I, [_P]),
+    "jmh_device_input_clamped": (_I, [_P, _P]),
+    "jmh_device_malloc": (_I, [_P, ctypes.c_size_t, _P]),
+    "jmh_device_free": (_I, [_P, _P]),
+    "jmh_device_upload": (_I, [_P, _P, _P, ctypes.c_size_t, _P]),
+    "jmh_device_stream_create": (_I, [_P, _P]),
+    "jmh_device_stream_destroy": (_I, [_P, _P]),
+}
+EXPORTED_INPUT = tuple(_SIGS_INPUT)
+
+
+def _addr(p):
+    """A device address: an int, or any object with data_ptr() (a torch tensor, for one; that
+    interoperation is not tested: the tests here do not load a second HIP runtime)."""
+    return int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)
+
+
+class DevicePicture:
+    """jmh_device_picture: format (JMH_PIX_*), the source size in luma samples, the planes' device
+    addresses (ints or objects with data_ptr(); two for NV12 / P010), their strides in bytes, and
+    the stream (Encoder.device_stream, or None) on which the planes are complete."""
+
+    def __init__(self, format, width, height, planes, strides, stream=None):
+        self.format, self.width, self.height = format, width, height
+        self.planes, self.strides, self.stream = list(planes), list(strides), stream
+
+    def struct(self):
+        s = JmhDevicePicture(self.format, self.width, self.height)
+        for i, (p, st) in enumerate(zip(self.planes, self.strides)):
+            s.plane[i] = _addr(p) if p is not None else None
+            s.stride[i] = st
+        s.stream = self.stream
+        return s
+
+
+class HostLayout:
+    """What to_device lays out: buf (uint8, to be uploaded as one block), the planes' byte offsets
+    in it and their strides."""
+
+    def __init__(self, format, width, height, buf, offsets, strides):
+        self.format, self.width, self.height, self.buf, self.offsets, self.strides = format, width, height, buf, offsets, strides
+
+    def at(self, base, stream=None):
+        """The DevicePicture of this layout uploaded at device address base."""
+        return DevicePicture(self.format, self.width, self.height, [_addr(base) + o for o in self.offsets], self.strides, stream)
+
+
+def to_device(pics, format, pad_stride=0, misalign=0):
+    """A numpy picture pics = (y, u, v) of the source size (h x w, h/2 x w/2 twice) laid out in the
+    requested format as a HostLayout.  pad_stride: bytes added to every row (filled with 0xA5, as
+    is everything between the planes); misalign: the offset in bytes of every plane's first sample
+    from a 256-byte boundary of the block.  P010 gets noise in the low 6 bits of every word."""
+    wide, semi = format >= JMH_PIX_I010, format in (JMH_PIX_NV12, JMH_PIX_P010)
+    dt = np.uint16 if wide else np.uint8
+    y, u, v = (np.ascontiguousarray(a, dt) for a in pics)
+    h, w = y.shape
+    if format == JMH_PIX_P010:
+        noise = lambda a: (np.arange(a.size, dtype=np.uint32).reshape(a.shape) * 37 + 11) & 63
+        y, u, v = ((a.astype(np.uint32) << 6 | noise(a)).astype(np.uint16) for a in (y, u, v))
+    if semi:
+        uv = np.empty((h // 2, w), dt)
+        uv[:, 0::2], uv[:, 1::2] = u, v
+        planes = [y, uv]
+    else:
+        planes = [y, u, v]
+    offsets, strides, end = [], [], 0
+    for a in planes:
+        rb = a.shape[1] * a.itemsize
+        offsets.append((end + 255) // 256 * 256 + misalign)
+        strides.append(rb + pad_stride)
+        end = offsets[-1] + (a.shape[0] - 1) * strides[-1] + rb      # no byte behind the last row's samples
+    buf = np.full(end, 0xA5, np.uint8)
+    for a, o, st in zip(planes, offsets, strides):
+        rb = a.shape[1] * a.itemsize
+        rows = np.lib.stride_tricks.as_strided(buf[o:], (a.shape[0], rb), (st, 1))
+        rows[:] = a.view(np.uint8).reshape(a.shape[0], rb)
+    return HostLayout(format, w, h, buf, offsets, strides)
+
+
+def pad_to_coded(pics, cw, ch):
+    """host/yuv.c jm_pad_picture in numpy: (y, u, v) of the source size replicated to cw x ch."""
+    out = []
+    for a, (H, W) in zip(pics, ((ch, cw), (ch // 2, cw // 2), (ch // 2, cw // 2))):
+        out.append(np.pad(a, ((0, H - a.shape[0]), (0, W - a.shape[1])), mode="edge"))
+    return tuple(out)
+
+
 def coded_slice_descs(nmb, slice_type, qp, mbs_per_slice=0, lead=()):
     """The descriptors of a coded picture (a JmhCodedSlice array), from the two writers' helpers:
     the raster runs and lead bits of slice_descs, the slice QPs of cabac_slice_descs."""
@@ -286,7 +386,7 @@ def load(path=LIB_PATH):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()) + \
-            list(_SIGS_CABAC_SPLIT.items()):
+            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -463,6 +563,77 @@ class Encoder:
         self._coded_n.pop(0)
         data = [out[w.offset:w.offset + w.nbytes].tobytes() for w in where]
         return data, wl, {"ssd": tuple(int(x) for x in stats.ssd), "fallback": int(stats.fallback)}
+
+    # ---- pictures that are already on the device (include/jmhip_input.h) ----
+    def device_alloc(self, nbytes):
+        """jmh_device_malloc: a device address (int)."""
+        p = ctypes.c_void_p()
+        _check(self.lib.jmh_device_malloc(self.ctx, nbytes, ctypes.byref(p)), "jmh_device_malloc")
+        return p.value
+
+    def device_free(self, addr):
+        _check(self.lib.jmh_device_free(self.ctx, _addr(addr)), "jmh_device_free")
+
+    def device_stream(self):
+        """jmh_device_stream_create: a stream handle (int) for DevicePicture.stream / device_upload."""
+        p = ctypes.c_void_p()
+        _check(self.lib.jmh_device_stream_create(self.ctx, ctypes.byref(p)), "jmh_device_stream_create")
+        return p.value
+
+    def device_stream_destroy(self, stream):
+        _check(self.lib.jmh_device_stream_destroy(self.ctx, stream), "jmh_device_stream_destroy")
+
+    def device_upload(self, dst, data, stream=None):
+        """jmh_device_upload: the bytes of a numpy array to device address dst, queued on stream
+        (None: done on return).  data is free on return either way."""
+        data = np.ascontiguousarray(data)
+        _check(self.lib.jmh_device_upload(self.ctx, _addr(dst), _ptr(data), data.nbytes, stream), "jmh_device_upload")
+
+    def device_picture(self, layout, stream=None, base=None):
+        """A HostLayout (to_device) uploaded: into base, or into a new allocation of exactly its
+        bytes (the caller frees .base).  Returns the DevicePicture."""
+        if base is None:
+            base = self.device_alloc(layout.buf.nbytes)
+        self.device_upload(base, layout.buf, stream)
+        pic = layout.at(base, stream)
+        pic.base = base
+        return pic
+
+    def push_device(self, pic, slice_type, qp, chroma_qp_offset=0, deblock=None):
+        """jmh_frame_push_device: push() of a DevicePicture; the library pads it to the coded size."""
+        fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
+        s = pic.struct()
+        _check(self.lib.jmh_frame_push_device(self.ctx, ctypes.byref(s), ctypes.byref(fp)), "jmh_frame_push_device")
+
+    def push_coded_device(self, pic, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0):
+        """jmh_frame_push_coded_device: push_coded() of a DevicePicture."""
+        fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
+        cw, ch = crop if crop is not None else (self.w, self.h)
+        self._coded_n = getattr(self, "_coded_n", [])
+        s = pic.struct()
+        _check(self.lib.jmh_frame_push_coded_device(self.ctx, ctypes.byref(s), ctypes.byref(fp), len(descs), ctypes.cast(descs, _P), cw, ch),
+               "jmh_frame_push_coded_device")
+        self._coded_n.append(len(descs))
+
+    def ingest(self, pic):
+        """jmh_ingest_picture, the unit seam: the DevicePicture packed and padded by the kernel, as
+        (y, u, v) of the coded size."""
+        y = np.empty((self.h, self.w), self.pdt)
+        u = np.empty((self.h // 2, self.w // 2), self.pdt)
+        v = np.empty_like(u)
+        s = pic.struct()
+        _check(self.lib.jmh_ingest_picture(self.ctx, ctypes.byref(s), _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2), "jmh_ingest_picture")
+        return y, u, v
+
+    def input_wait(self):
+        """jmh_device_input_wait: the last pushed device picture has been read; its planes are free."""
+        _check(self.lib.jmh_device_input_wait(self.ctx), "jmh_device_input_wait")
+
+    def input_clamped(self):
+        """jmh_device_input_clamped: I010 samples above maxv in the picture last popped (or last ingest)."""
+        n = ctypes.c_uint64()
+        _check(self.lib.jmh_device_input_clamped(self.ctx, ctypes.byref(n)), "jmh_device_input_clamped")
+        return n.value
 
     def pop_into(self, y, u, v):
         """What lencod does per picture: jmh_frame_pop, the results in place (a zero-copy view of the

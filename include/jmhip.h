@@ -37,7 +37,8 @@
  * SymbolMode 1 (CABAC): include/jmhip_cabac.h, included behind it, additive as well.
  * Coded pictures (a pipelined picture whose slice data is written behind its last macroblock and
  * whose pop returns the slice bytes and the distortion only): include/jmhip_coded.h, included
- * last, additive as well.
+ * last, additive as well.  Pictures that are already on the device (planar, NV12, P010; padded to
+ * the coded size by the library): include/jmhip_input.h, additive as well.
  *
  * Conventions: plain C types only; 0 = OK, negative JMH_E_* on error; nothing throws or aborts
  * across this boundary.  One context = one HIP device + one HIP stream; a context is not
@@ -380,4 +381,5 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #include "jmhip_cabac.h"
 #include "jmhip_coded.h"
 #include "jmhip_cabac_split.h"
+#include "jmhip_input.h"
 #endif /* JMHIP_H */
