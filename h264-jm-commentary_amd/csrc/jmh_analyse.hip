@@ -619,9 +619,10 @@ __device__ __forceinline__ void p8x8_block(const DevParams &d, MeS &s, PosState 
 // ======================================================================================
 //  intra decisions
 // ======================================================================================
-// the Intra16x16 decision of the RDO-off wavefront (MbScratch i16cost / i16mode)
-template <class pel>
-__device__ __forceinline__ void i16_decision(const DevParams &d, const pel *org, const IntraNb<pel> &nb, MbScratch *scr, int lane, bool avL, bool avT,
+// the Intra16x16 decision of the RDO-off wavefront (i16cost / i16mode of SC: MbScratch, or
+// k_mb_flow's MbCarry in LDS)
+template <class pel, class SC>
+__device__ __forceinline__ void i16_decision(const DevParams &d, const pel *org, const IntraNb<pel> &nb, SC *scr, int lane, bool avL, bool avT,
                                              bool avTL) {
     int best, i16mode;
     i16_pick(d, org, nb, lane, avL, avT, avTL, best, i16mode);
@@ -631,8 +632,8 @@ __device__ __forceinline__ void i16_decision(const DevParams &d, const pel *org,
 // IntraChromaPrediction8x8 mode decision on one wave: 4 modes x 2 components x 4 blocks.  A lane's
 // DC and plane parameters once, then each sample selected without branching (a per-lane mode
 // switch ran all four paths, the plane's parameters per sample)
-template <class pel>
-__device__ __forceinline__ void chroma_decision(const DevParams &d, const IntraNb<pel> &nb, MbScratch *scr, int lane, bool avL, bool avT, bool avTL) {
+template <class pel, class SC>
+__device__ __forceinline__ void chroma_decision(const DevParams &d, const IntraNb<pel> &nb, SC *scr, int lane, bool avL, bool avT, bool avTL) {
     int sat = 0;
     if (lane < 32) {
         const int m = lane >> 3, uv = (lane >> 2) & 1, b = lane & 3, xo = (b & 1) * 4, yo = (b >> 1) * 4;
@@ -672,7 +673,8 @@ __device__ __forceinline__ void chroma_decision(const DevParams &d, const IntraN
 // ======================================================================================
 //  motion search of one P macroblock (all 41 searches)
 // ======================================================================================
-__device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &s, MbScratch *scr, int k, int w, int mbx, int mby);
+template <class SC>
+__device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &s, SC *scr, int16_t (*i4lev)[16], int k, int w, int mbx, int mby);
 
 // the part of me_mb's setup that reads no other workgroup's output (the source block, the lambda *
 // mvbits table, zeroed accumulators): k_mb_flow runs it while its dependencies finish (pre = true
@@ -685,14 +687,17 @@ __device__ __forceinline__ void me_prologue(const DevParams &d, MeS &s, int mbx,
     for (int i = tid; i < MVB_LEN; i += NTA) s.mvc[i] = (uint16_t)__umul24(d.lambda_motion, mvbits(i - MVB_OFF));
 }
 
-__device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, int mbx, int mby, bool pre = false) {
+// scr: where the results go.  MbScratch (the tick kernels): everything, for k_mb_final in HBM.
+// MbCarry (k_mb_flow, in LDS): only the scalars; the final reads the rest in s, and the Intra4x4
+// levels in i4lev
+template <class SC>
+__device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, SC *scr, int16_t (*i4lev)[16], int mbx, int mby, bool pre = false) {
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // an SGPR: tid itself dies after the setup
     const int W = d.W, sr = d.sr, side = d.side;
     const int pix_x = 16 * mbx, pix_y = 16 * mby;
     const bool prof = prof_mb_here(d, mbx, mby);
     PSTAMP(0);
-    MbScratch *scr = d.scr + mby * d.mbw + mbx;
     if (tid == 0) { s.pst = prof ? d.prof + 20 : nullptr; s.pn = 0; }
     if (tid < 256) { if (!pre) s.in.org[tid] = s.org[tid] = d.orgY[(pix_y + (tid >> 4)) * W + pix_x + (tid & 15)]; }
     else if (tid >= 384 && tid < 394) { load_border(d, s.bd, tid - 384, mbx, mby); load_border(d, s.in.bd, tid - 384, mbx, mby); }
@@ -700,7 +705,7 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, int mbx, int m
     else if (!pre && tid >= 480 && tid < 512) s.motion_cost[(tid - 480) >> 2][tid & 3] = 0;
     // the MB's Intra4x4 decision (10 diagonal steps, then the results) runs on waves 6 and 7
     // while the motion search's sub-pel waves work: slots 0..10 (intra_slot)
-    auto idle = [&](int k, int w) { intra_slot(d, s.in, scr, k, w, mbx, mby); };
+    auto idle = [&](int k, int w) { intra_slot(d, s.in, scr, i4lev, k, w, mbx, mby); };
     if (!pre)
         for (int i = tid; i < MVB_LEN; i += NTA) s.mvc[i] = (uint16_t)__umul24(d.lambda_motion, mvbits(i - MVB_OFF));
     int pcx = 0, pcy = 0, scx = 0, scy = 0;
@@ -844,14 +849,18 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, int mbx, int m
             p8x8_block<2>(d, s, ps, best8x8, cost8x8, idle, wave, tid);
             PSTAMP(5);
             p8x8_block<3>(d, s, ps, best8x8, cost8x8, idle, wave, tid);
-            // results: MVs of types 1..7, partition costs, P8x8 modes, FindSkipModeMotionVector
-            if (tid < 224) {
-                const int m = 1 + tid / 32, k = (tid & 31) >> 1, c = tid & 1;
-                scr->all_mv[m][k][c] = s.all_mv[m][k][c];
-            } else if (tid < 252) {
-                const int m = 1 + (tid - 224) / 4, k = tid & 3;
-                scr->motion_cost[m][k] = s.motion_cost[m][k];
-            } else if (tid == 256) {
+            // results: MVs of types 1..7, partition costs (k_mb_flow's final reads both in s), P8x8
+            // modes, FindSkipModeMotionVector
+            if constexpr (scr_global<SC>) {
+                if (tid < 224) {
+                    const int m = 1 + tid / 32, k = (tid & 31) >> 1, c = tid & 1;
+                    scr->all_mv[m][k][c] = s.all_mv[m][k][c];
+                } else if (tid < 252) {
+                    const int m = 1 + (tid - 224) / 4, k = tid & 3;
+                    scr->motion_cost[m][k] = s.motion_cost[m][k];
+                }
+            }
+            if (tid == 256) {
                 scr->best8x8 = best8x8; scr->cost8x8 = cost8x8;
             } else if (tid == 320) {
                 NbBorder nbv{s.bd};
@@ -867,9 +876,10 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, int mbx, int m
 }
 
 // one MB on 128 threads (tid = 0..127, waves 0 and 1 of the group); every thread of the
-// workgroup reaches the same barriers (act: the group has an MB)
-template <class pel>
-__device__ __forceinline__ void intra_role(const DevParams &d, IntraS<pel> &s, int mbx, int mby, int tid, bool act, bool i4) {
+// workgroup reaches the same barriers (act: the group has an MB).  scr, i4lev: as for me_mb
+template <class pel, class SC>
+__device__ __forceinline__ void intra_role(const DevParams &d, IntraS<pel> &s, SC *scr, int16_t (*i4lev)[16], int mbx, int mby, int tid, bool act,
+                                           bool i4) {
     const int wave = tid >> 6, lane = tid & 63;
     const int pix_x = 16 * mbx, pix_y = 16 * mby, W = d.W;
     const MbAvail mav = intra_avail(d, mbx, mby);
@@ -884,7 +894,6 @@ __device__ __forceinline__ void intra_role(const DevParams &d, IntraS<pel> &s, i
         if (tid < 10) load_border(d, s.bd, tid, mbx, mby);
         else if (tid >= 16 && tid < 16 + 71) load_intra_nb(d, s.nb, tid - 16, mbx, mby);
     }
-    MbScratch *scr = d.scr + mby * d.mbw + mbx;
     const int q_bits = 15 + (d.qp + d.qpbd) / 6;
     const int qpk = q_round(d.qsel, q_bits);
     int tabr[2];
@@ -894,7 +903,7 @@ __device__ __forceinline__ void intra_role(const DevParams &d, IntraS<pel> &s, i
     for (int dg = 0; dg < 10; dg++) {         // blocks with bx4 + 2*by4 == dg, by4 ascending
         const int by_lo = dg > 3 ? (dg - 2) >> 1 : 0;
         const int by4 = by_lo + wave, bx4 = dg - 2 * by4;
-        if (act && i4 && by4 <= 3 && bx4 >= 0 && bx4 <= 3) i4_block(d, s, scr, wave, bx4, by4, tabr, avL, avT, avTL, avTR, qpk, acc);
+        if (act && i4 && by4 <= 3 && bx4 >= 0 && bx4 <= 3) i4_block(d, s, i4lev, wave, bx4, by4, tabr, avL, avT, avTL, avTR, qpk, acc);
         __syncthreads();
     }
     if (act && lane == 0) { s.part[wave][0] = acc[0]; s.part[wave][1] = acc[1]; s.part[wave][2] = acc[2]; }
@@ -905,8 +914,10 @@ __device__ __forceinline__ void intra_role(const DevParams &d, IntraS<pel> &s, i
         scr->i4cbp = s.part[0][1] | s.part[1][1];
         scr->i4blk = s.part[0][2] | s.part[1][2];
     }
-    if (i4 && tid < 16) scr->ipred[tid] = s.ipred_cur[tid];
-    if (i4 && tid < (int)sizeof(s.rec) / 4) reinterpret_cast<uint32_t *>(scr->i4rec)[tid] = reinterpret_cast<const uint32_t *>(s.rec)[tid];
+    if constexpr (scr_global<SC>) {           // (k_mb_flow's final reads both in s)
+        if (i4 && tid < 16) scr->ipred[tid] = s.ipred_cur[tid];
+        if (i4 && tid < (int)sizeof(s.rec) / 4) reinterpret_cast<uint32_t *>(scr->i4rec)[tid] = reinterpret_cast<const uint32_t *>(s.rec)[tid];
+    }
     PSTAMP(13);
     // Intra16x16 (wave 0) and intra chroma mode (wave 1) decisions
     if (wave == 0) i16_decision(d, s.org, s.nb, scr, lane, avL, avT, avTL);
@@ -919,7 +930,8 @@ __device__ __forceinline__ void intra_role(const DevParams &d, IntraS<pel> &s, i
 // by the stage barriers.  Slot
 // k = 0..9: diagonal k of the 4x4 grid; slot 10: the totals and results; slot 11 (k_mb_flow, on
 // wave 3): the Intra16x16 (w = 0) or the chroma intra-mode (w = 1) decision.
-__device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &s, MbScratch *scr, int k, int w, int mbx, int mby) {
+template <class SC>
+__device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &s, SC *scr, int16_t (*i4lev)[16], int k, int w, int mbx, int mby) {
     const int lane = threadIdx.x & 63;
     const MbAvail mav = intra_avail(d, mbx, mby);
     const bool avL = mav.L, avT = mav.T, avTL = mav.TL, avTR = mav.TR;
@@ -938,7 +950,7 @@ __device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &
         if (by4 <= 3 && bx4 >= 0 && bx4 <= 3) {   // the wave's running cost / cbp / block mask live in LDS
             int acc[3] = {s.part[w][0], s.part[w][1], s.part[w][2]};
             unsigned long long *pst = (k == 4 && w == 0 && d.prof && d.prof_mb == mby * d.mbw + mbx) ? d.prof : nullptr;   // debug stamps
-            i4_block(d, s, scr, w, bx4, by4, tabr, avL, avT, avTL, avTR, qpk, acc, pst);
+            i4_block(d, s, i4lev, w, bx4, by4, tabr, avL, avT, avTL, avTR, qpk, acc, pst);
             if (lane == 0) { s.part[w][0] = acc[0]; s.part[w][1] = acc[1]; s.part[w][2] = acc[2]; }
         }
     } else if (w == 0) {
@@ -947,8 +959,10 @@ __device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &
             scr->i4cbp = s.part[0][1] | s.part[1][1];
             scr->i4blk = s.part[0][2] | s.part[1][2];
         }
-        if (lane < 16) scr->ipred[lane] = s.ipred_cur[lane];
-        reinterpret_cast<uint32_t *>(scr->i4rec)[lane] = reinterpret_cast<const uint32_t *>(s.rec)[lane];
+        if constexpr (scr_global<SC>) {
+            if (lane < 16) scr->ipred[lane] = s.ipred_cur[lane];
+            reinterpret_cast<uint32_t *>(scr->i4rec)[lane] = reinterpret_cast<const uint32_t *>(s.rec)[lane];
+        }
     }
 }
 
@@ -971,14 +985,16 @@ __global__ __launch_bounds__(NTA, 4) void k_mb_analyse(const TickArgs t) {
         const DevParams d = tick_params(t, e);
         const int mby = d.y_min + (m - t.pre[e]), mbx = d.diag - 2 * mby;
         tag = 2u | (unsigned long long)(mby * d.mbw + mbx) << 4 | (unsigned long long)e << 32;
-        me_mb(d, s.me, mbx, mby);
+        MbScratch *scr = d.scr + mby * d.mbw + mbx;
+        me_mb(d, s.me, scr, scr->i4lev, mbx, mby);
     } else {
         const int q = __builtin_amdgcn_readfirstlane(4 * (b - nPg) + (int)(threadIdx.x >> 7));
         const bool act = q < tot;
         const int e = tick_entry(t, act ? q : 0);
         const DevParams d = tick_params(t, e);
         const int mby = d.y_min + ((act ? q : t.pre[e]) - t.pre[e]), mbx = d.diag - 2 * mby;
-        intra_role(d, s.in[threadIdx.x >> 7], mbx, mby, threadIdx.x & 127, act, q >= nPm);
+        MbScratch *scr = d.scr + mby * d.mbw + mbx;
+        intra_role(d, s.in[threadIdx.x >> 7], scr, scr->i4lev, mbx, mby, threadIdx.x & 127, act, q >= nPm);
     }
     if (t.bprof) {
         __syncthreads();
@@ -1012,7 +1028,8 @@ __global__ __launch_bounds__(NT, JMH_INTRA_OCC) void k_mb_intra(const TickArgs t
         const int e = tick_entry(t, act ? q : 0);
         const DevParams d = tick_params(t, e);
         const int mby = d.y_min + ((act ? q : t.pre[e]) - t.pre[e]), mbx = d.diag - 2 * mby;
-        intra_role(d, s.in[threadIdx.x >> 7], mbx, mby, threadIdx.x & 127, act, true);
+        MbScratch *scr = d.scr + mby * d.mbw + mbx;
+        intra_role(d, s.in[threadIdx.x >> 7], scr, scr->i4lev, mbx, mby, threadIdx.x & 127, act, true);
     } else {
         const int mi = xcd_block(b - nRg, tot);
         if (mi >= tot) return;
@@ -1041,26 +1058,37 @@ hipError_t jmh_launch_analyse(const TickArgs &t, hipStream_t st) {
 // ======================================================================================
 //  k_mb_flow: the dataflow wavefront (jmh_device.h FlowArgs)
 // ======================================================================================
+// a kernel argument as a scalar register of its own: the eight ints W .. restrict_sr arrive in one
+// 8-dword load, and a register tuple that spills is reloaded whole wherever one member is read
+// (1100 v_readlane in the search stages when the allocator chose to)
+__device__ __forceinline__ int own_sgpr(int v) {
+    asm("" : "+s"(v));
+    return v;
+}
+
 __device__ __forceinline__ DevParams flow_params(const FlowArgs &f, const PicParams &q) {
     DevParams d;
-    d.W = f.W; d.H = f.H; d.Wc = f.W >> 1; d.Hc = f.H >> 1; d.mbw = f.mbw; d.mbh = f.mbh;
-    d.sr = f.sr; d.side = 2 * f.sr + 1; d.npos = d.side * d.side;
-    d.search_mode = f.search_mode; d.use_hadamard = f.use_hadamard; d.restrict_sr = f.restrict_sr;
+    const int W = own_sgpr(f.W), H = own_sgpr(f.H), sr = own_sgpr(f.sr);
+    d.W = W; d.H = H; d.Wc = W >> 1; d.Hc = H >> 1; d.mbw = own_sgpr(f.mbw); d.mbh = own_sgpr(f.mbh);
+    d.sr = sr; d.side = 2 * sr + 1; d.npos = d.side * d.side;
+    d.search_mode = own_sgpr(f.search_mode); d.use_hadamard = own_sgpr(f.use_hadamard); d.restrict_sr = own_sgpr(f.restrict_sr);
     d.isr = f.isr;
     d.t8 = 0;
     d.epzs_dual = 0; d.epzs_subpel = 0; d.epzs_spts = 0; d.epzs_mints = 0; d.epzs_maxts = 0;
     d.slice_mbs = f.slice_mbs;
     d.maxv = 255; d.qpbd = 0;
-    const int ls = f.W * f.H, lc = ls >> 2;
+    const int ls = W * H, lc = ls >> 2;
     d.orgY = q.org; d.orgU = q.org + ls; d.orgV = q.org + ls + lc;
     d.refY = q.ref; d.refU = q.ref + ls; d.refV = q.ref + ls + lc;
     d.recY = q.rec; d.recU = q.rec + ls; d.recV = q.rec + ls + lc;
     d.dbkY = q.dbk; d.dbkU = q.dbk ? q.dbk + ls : nullptr; d.dbkV = q.dbk ? q.dbk + ls + lc : nullptr;
     d.lf_disable = q.lf_disable; d.lf_offA = q.lf_offA; d.lf_offB = q.lf_offB;
-    d.mv = q.mv; d.refidx = q.refidx; d.ipred = q.ipred; d.res = q.res; d.scr = q.scr;
+    d.mv = q.mv; d.refidx = q.refidx; d.ipred = q.ipred; d.res = q.res;
+    d.scr = nullptr;                                     // (the analysis' results stay in LDS: FlowAnalysis)
     d.tmv = nullptr; d.tref = nullptr; d.ordtab = f.ordtab;
     d.prof = f.prof; d.prof_mb = f.prof_mb;
-    d.slice_type = q.slice_type; d.qp = q.qp; d.lambda_mode = q.lambda_mode; d.lambda_motion = q.lambda_motion;
+    d.slice_type = q.slice_type; d.qp = q.qp; d.lambda_motion = q.lambda_motion;
+    d.lambda_mode = __builtin_amdgcn_readfirstlane(q.lambda_mode);   // an SGPR: a VGPR held across me_mb spilled
     d.cqp_off = q.cqp_off; d.qsel = q.qsel; d.diag = q.diag; d.y_min = q.y_min;
     d.rdo = 0; d.cavlc = 0;
     d.i16c = 1;
@@ -1102,6 +1130,37 @@ struct PlaneMC {
     }
 };
 
+// k_mb_flow's view of the analysis results for final_core (ScratchAnalysis, jmh_final.h), over the
+// workgroup's LDS: the P macroblock's MVs and partition costs in its MeS, the Intra4x4 modes and
+// reconstruction in the MB's IntraS, the Intra4x4 levels in the final's own level array, the rest
+// in the MbCarry.  (No Intra8x8 in the dataflow path: T8 = false.)
+struct FlowAnalysis {
+    const MeS &me;
+    const IntraS<uint8_t> &in;
+    const MbCarry &c;
+    const int16_t (*lev)[16];
+    __device__ __forceinline__ int motion_cost(int m, int k) const { return me.motion_cost[m][k]; }
+    __device__ __forceinline__ int mv(int m, int k, int cc) const { return me.all_mv[m][k][cc]; }
+    __device__ __forceinline__ int best8x8() const { return c.best8x8; }
+    __device__ __forceinline__ int cost8x8() const { return c.cost8x8; }
+    __device__ __forceinline__ int skipx() const { return c.skipx; }
+    __device__ __forceinline__ int skipy() const { return c.skipy; }
+    __device__ __forceinline__ int i4cost() const { return c.i4cost; }
+    __device__ __forceinline__ int i4cbp() const { return c.i4cbp; }
+    __device__ __forceinline__ int i4blk() const { return c.i4blk; }
+    __device__ __forceinline__ int i4lev(int blk, int l) const { return lev[blk][l]; }
+    __device__ __forceinline__ uint8_t i4rec(int i) const { return in.rec[i]; }
+    __device__ __forceinline__ int ipred(int k) const { return in.ipred_cur[k]; }
+    __device__ __forceinline__ int i16cost() const { return c.i16cost; }
+    __device__ __forceinline__ int i16mode() const { return c.i16mode; }
+    __device__ __forceinline__ int c_mode() const { return c.c_mode; }
+    __device__ __forceinline__ int i8cost() const { return 0; }
+    __device__ __forceinline__ int i8cbp() const { return 0; }
+    __device__ __forceinline__ int i8modes() const { return 0; }
+    __device__ __forceinline__ int i8lev(int, int) const { return 0; }
+    __device__ __forceinline__ uint8_t i8rec(int) const { return 0; }
+};
+
 #define FLOW_SPIN_MAX (1 << 17)               // polls before a dependency wait gives up (~0.1 s; a wait
                                               // lasts a few macroblocks, ~0.2 ms, at most)
 __device__ __forceinline__ bool flow_done(const FlowArgs &f, int e, int mb, uint32_t gen) {
@@ -1115,17 +1174,21 @@ __device__ __forceinline__ bool flow_done(const FlowArgs &f, int e, int mb, uint
 // be done -- the rest of the wavefront's dependencies follow from theirs; a claimed ticket belongs
 // to a running workgroup and waits only on smaller tickets, so every wait ends.  Then the P
 // macroblock's me_mb (41 searches + Intra4x4, and its Intra16x16 / chroma decisions on wave 3
-// beside two search stages; an I macroblock: intra_role), and final_core on all 512 threads.
+// beside two search stages; an I macroblock: intra_role), and final_core on all 512 threads, which
+// reads the analysis' results where they lie in LDS (FlowAnalysis): the kernel stores nothing to
+// MbScratch.
 // Publication: every wave's stores
 // drained, the workgroup barrier, one agent-scope release, the flag; a waiter polls relaxed, then
 // one agent-scope acquire before the workgroup reads (MI355X_MICROARCH.md, inter-workgroup
 // visibility).
 __global__ __launch_bounds__(NTA, 4) void k_mb_flow(const FlowArgs f) {
-    // the final's LDS beside the analysis' (81.1 KB: still two workgroups per CU), so that it reads
-    // the MB's source, intra neighbourhood and search window planes where the analysis left them
+    // the final's LDS beside the analysis' (81.2 KB: still two workgroups per CU), so that it reads
+    // the MB's source, intra neighbourhood, search window planes and analysis results where the
+    // analysis left them (fin.lev, idle until the final, takes the Intra4x4 levels)
     __shared__ struct {
         FinS<uint8_t> fin;
         AnalyseS a;
+        MbCarry carry;
     } s;
     __shared__ int s_item;
     __shared__ unsigned s_tk;
@@ -1185,8 +1248,8 @@ __global__ __launch_bounds__(NTA, 4) void k_mb_flow(const FlowArgs f) {
     }
     {   // the analysis (DevParams scoped per phase: one set live across me_mb spills)
         const DevParams d = flow_params(f, f.pics[e].pp);
-        if (pslice) me_mb(d, s.a.me, mbx, mby, true);
-        else intra_role(d, s.a.in[tid >> 7], mbx, mby, tid & 127, tid < 128, true);
+        if (pslice) me_mb(d, s.a.me, &s.carry, s.fin.lev, mbx, mby, true);
+        else intra_role(d, s.a.in[tid >> 7], &s.carry, s.fin.lev, mbx, mby, tid & 127, tid < 128, true);
     }
     if (unsigned long long *fp = FLOW_FP; fp && tid == 0) fp[2] = wall_clock64();
     asm volatile("" ::: "memory");                            // re-read the parameters below
@@ -1194,14 +1257,14 @@ __global__ __launch_bounds__(NTA, 4) void k_mb_flow(const FlowArgs f) {
         const DevParams d = flow_params(f, f.pics[e].pp);
         const bool prof = prof_mb_here(d, mbx, mby);
         PSTAMP(56);
-        __syncthreads();                                      // MbScratch complete
+        __syncthreads();                                      // the analysis' results complete (in LDS)
         PSTAMP(58);
         int pcx = 0, pcy = 0;                                 // me_mb's window origin (SetupFastFullPelSearch centre)
         if (pslice) set_mvp(NbBorder{s.a.me.bd}, 0, 0, 16, 16, pcx, pcy);
         const int scx = iclip(-d.sr, d.sr, pcx / 4), scy = iclip(-d.sr, d.sr, pcy / 4);
         const PlaneMC mc{(uint32_t)(uintptr_t)(lds_cu8 *)s.a.me.planes, 16 * mbx + scx - d.sr - WM, 16 * mby + scy - d.sr - WM};
         IntraS<uint8_t> &in = pslice ? s.a.me.in : s.a.in[0];  // (I macroblocks: no MC)
-        final_core<5, uint8_t, false, NTA>(d, s.fin, mbx, mby, tid, mc, in.org, &in.nb);
+        final_core<5, uint8_t, false, NTA>(d, s.fin, mbx, mby, tid, mc, FlowAnalysis{s.a.me, in, s.carry, s.fin.lev}, in.org, &in.nb);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();

@@ -54,6 +54,21 @@ struct MbScratch {
     alignas(4) uint8_t i8rec[512];
 };
 
+// k_mb_flow hands a macroblock's analysis to its final inside the workgroup, in LDS: the MVs, costs,
+// Intra4x4 modes and reconstruction stay where the analysis computed them (MeS, IntraS), the
+// Intra4x4 levels go straight into the final's level array, and these words carry the scalars that
+// have no other LDS home (the MbScratch members of the same names).  The analysis functions take
+// either struct as their destination (scr_global: which one).
+struct MbCarry {
+    int32_t best8x8, cost8x8;
+    int32_t skipx, skipy;
+    int32_t i4cost, i4cbp, i4blk;
+    int32_t i16cost, i16mode, c_mode;
+};
+template <class SC> struct ScrKind { static constexpr bool global = false; };
+template <> struct ScrKind<MbScratch> { static constexpr bool global = true; };
+template <class SC> constexpr bool scr_global = ScrKind<SC>::global;
+
 // RDOptimization 1: the per-picture RD state, stored right after the picture's MbScratch array
 // (PicParams.scr + mbw * mbh) so that the kernel arguments stay within 4 KB: the lambdas from the
 // host, the slices' CABAC states (contexts + codIRange, jmh_cabac_rate.h) and what every coded

@@ -42,6 +42,35 @@ struct FinS {
     DbkS<pel> db;                        // the fused deblocking (jmh_deblock.h)
 };
 
+// The macroblock's analysis results as final_core reads them, behind a view (AV).  This one reads
+// the MbScratch the tick kernels' analysis left in HBM; k_mb_flow's reads the analysis state still
+// in its workgroup's LDS (FlowAnalysis, jmh_analyse.hip).
+template <class pel>
+struct ScratchAnalysis {
+    const MbScratch *sc;
+    __device__ __forceinline__ int motion_cost(int m, int k) const { return sc->motion_cost[m][k]; }
+    __device__ __forceinline__ int mv(int m, int k, int c) const { return sc->all_mv[m][k][c]; }
+    __device__ __forceinline__ int best8x8() const { return sc->best8x8; }
+    __device__ __forceinline__ int cost8x8() const { return sc->cost8x8; }
+    __device__ __forceinline__ int skipx() const { return sc->skipx; }
+    __device__ __forceinline__ int skipy() const { return sc->skipy; }
+    __device__ __forceinline__ int i4cost() const { return sc->i4cost; }
+    __device__ __forceinline__ int i4cbp() const { return sc->i4cbp; }
+    __device__ __forceinline__ int i4blk() const { return sc->i4blk; }
+    __device__ __forceinline__ int i4lev(int blk, int l) const { return sc->i4lev[blk][l]; }
+    __device__ __forceinline__ pel i4rec(int i) const { return spl<pel>(sc->i4rec)[i]; }
+    __device__ __forceinline__ int ipred(int k) const { return sc->ipred[k]; }
+    __device__ __forceinline__ int i16cost() const { return sc->i16cost; }
+    __device__ __forceinline__ int i16mode() const { return sc->i16mode; }
+    __device__ __forceinline__ int c_mode() const { return sc->c_mode; }
+    // Intra8x8 (Transform8x8Mode)
+    __device__ __forceinline__ int i8cost() const { return sc->i8cost; }
+    __device__ __forceinline__ int i8cbp() const { return sc->i8cbp; }
+    __device__ __forceinline__ int i8modes() const { return sc->i8modes; }
+    __device__ __forceinline__ int i8lev(int blk, int l) const { return sc->i8lev[blk][l]; }
+    __device__ __forceinline__ pel i8rec(int i) const { return spl<pel>(sc->i8rec)[i]; }
+};
+
 // OCC (k_mb_final) workgroups per CU: 8 (64 VGPRs, a few spilled) for ticks of more than 5 x 256 MBs (2160p,
 // one dispatch round), 5 (no spills, a shorter per-MB chain) for smaller ticks
 // T8: built with Transform8x8Mode's paths (I8MB, TransformDecision, dct_luma8x8); the
@@ -53,9 +82,9 @@ struct FinS {
 // mc(X, Y): the luma sample at quarter-pel position (X, Y) of the reference (qpel_direct from HBM in
 // the tick kernels; k_mb_flow reads its search window's G / b / h / j planes in LDS).  porg / pnb:
 // the MB's source and intra neighbourhood already in LDS (k_mb_flow's analysis state), or null:
-// loaded here.
-template <int OCC, class pel, bool T8, int NTH, class MC>
-__device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, int mby, int tid, MC mc, const pel *porg = nullptr,
+// loaded here.  an: the analysis results (ScratchAnalysis above, or k_mb_flow's view of its LDS).
+template <int OCC, class pel, bool T8, int NTH, class MC, class AV>
+__device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, int mby, int tid, MC mc, AV an, const pel *porg = nullptr,
                                            const IntraNb<pel> *pnb = nullptr) {
     constexpr bool W2 = NTH == 512;
     static_assert(NTH == 256 || NTH == 512, "final_core runs on 256 or 512 threads");
@@ -76,7 +105,6 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     const bool avL = mav.L, avT = mav.T, avTL = mav.TL;
     const bool prof = prof_mb_here(d, mbx, mby);
     PSTAMP(16);
-    const MbScratch *sc = d.scr + mby * d.mbw + mbx;
 
     // ---- inputs into LDS (unless the caller's LDS holds them)
     const pel *S_org = porg ? porg : s.org;
@@ -113,18 +141,18 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     if (slice_p) {
         for (int mode = 1; mode < 4; mode++) {
             if (!inter_on(d.isr, mode)) continue;
-            const int cost = mode == 1 ? sc->motion_cost[1][0] : sc->motion_cost[mode][0] + sc->motion_cost[mode][1];
+            const int cost = mode == 1 ? an.motion_cost(1, 0) : an.motion_cost(mode, 0) + an.motion_cost(mode, 1);
             if (cost < min_cost) { best_mode = mode; min_cost = cost; }
         }
         if (inter_on(d.isr, 4) || inter_on(d.isr, 5) || inter_on(d.isr, 6) || inter_on(d.isr, 7)) {
-            best8x8 = sc->best8x8;
-            if (sc->cost8x8 < min_cost) { best_mode = JMH_P8x8; min_cost = sc->cost8x8; }
+            best8x8 = an.best8x8();
+            if (an.cost8x8() < min_cost) { best_mode = JMH_P8x8; min_cost = an.cost8x8(); }
         }
     }
-    if (d.t8 && sc->i8cost <= min_cost) { min_cost = sc->i8cost; best_mode = JMH_I8MB; }   // item 27
-    if (sc->i4cost <= min_cost) { min_cost = sc->i4cost; best_mode = JMH_I4MB; }
-    const int i16mode = sc->i16mode;
-    if (sc->i16cost < min_cost) { min_cost = sc->i16cost; best_mode = JMH_I16MB; }
+    if (d.t8 && an.i8cost() <= min_cost) { min_cost = an.i8cost(); best_mode = JMH_I8MB; }   // item 27
+    if (an.i4cost() <= min_cost) { min_cost = an.i4cost(); best_mode = JMH_I4MB; }
+    const int i16mode = an.i16mode();
+    if (an.i16cost() < min_cost) { min_cost = an.i16cost(); best_mode = JMH_I16MB; }
     const int is_intra = best_mode == JMH_I4MB || best_mode == JMH_I16MB || best_mode == JMH_I8MB;
     int b8mode[4];
     for (int b = 0; b < 4; b++)
@@ -133,13 +161,13 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     if (tid < 32) {
         const int k = tid >> 1, c = tid & 1, b8 = ((k >> 3) << 1) + ((k & 3) >> 1);
         const int bm = best_mode == JMH_P8x8 ? (best8x8 >> (4 * b8)) & 15 : best_mode;
-        s.fmv[k][c] = is_intra ? 0 : sc->all_mv[bm][k][c];
+        s.fmv[k][c] = is_intra ? 0 : an.mv(bm, k, c);
     }
     __syncthreads();
 
     // ======== chroma prediction, ahead of the luma: the inter prediction's reference reads then
     // travel with the luma MC's instead of one round trip after them
-    const int c_mode = is_intra ? sc->c_mode : 0;
+    const int c_mode = is_intra ? an.c_mode() : 0;
     const int l = tid & 15;
     const int cuv = (ct >> 4) >> 2, cb = (ct >> 4) & 3;
     const int cxo = (cb & 1) * 4 + (ct & 3), cyo = (cb >> 1) * 4 + ((ct & 15) >> 2);
@@ -215,18 +243,18 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     const int w8 = tid >> 6, l8 = tid & 63;                           // 8x8 layout: wave = 8x8 block
     const int qx = 8 * (w8 & 1) + (l8 & 7), qy = 8 * (w8 >> 1) + (l8 >> 3);
     if (best_mode == JMH_I8MB) {
-        cbp = sc->i8cbp; tr8 = true;
+        cbp = an.i8cbp(); tr8 = true;
         for (int b = 0; b < 4; b++)
             if ((cbp >> b) & 1) cbp_blk |= 0x33 << ((b >> 1) * 8 + (b & 1) * 2);
         if (lu) {
-            s.lev[blk][l] = sc->i8lev[blk][l];
-            s.rec[tid] = spl<pel>(sc->i8rec)[tid];
+            s.lev[blk][l] = (int16_t)an.i8lev(blk, l);
+            s.rec[tid] = an.i8rec(tid);
         }
     } else if (best_mode == JMH_I4MB) {
-        cbp = sc->i4cbp; cbp_blk = sc->i4blk;
+        cbp = an.i4cbp(); cbp_blk = an.i4blk();
         if (lu) {
-            s.lev[blk][l] = sc->i4lev[blk][l];
-            s.rec[tid] = spl<pel>(sc->i4rec)[tid];
+            s.lev[blk][l] = (int16_t)an.i4lev(blk, l);   // (k_mb_flow: already there)
+            s.rec[tid] = an.i4rec(tid);
         }
     } else if (best_mode == JMH_I16MB) {
         // dct_luma_16x16 [J] (jmh_intra.h i16_code)
@@ -347,7 +375,7 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     // ======== outputs: jmh_mb_result, reconstruction, picture MV / ref / Intra4x4-mode arrays
     jmh_mb_result *res = d.res + mby * d.mbw + mbx;
     int mb_type = best_mode;
-    if (slice_p && best_mode == 1 && cbp == 0 && s.fmv[0][0] == sc->skipx && s.fmv[0][1] == sc->skipy) mb_type = JMH_PSKIP;
+    if (slice_p && best_mode == 1 && cbp == 0 && s.fmv[0][0] == an.skipx() && s.fmv[0][1] == an.skipy()) mb_type = JMH_PSKIP;
     if (tid == 0) {
         res->mb_type = (int16_t)mb_type;
         res->cbp = (int16_t)cbp;
@@ -365,8 +393,8 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     if (lu) res->luma[blk][l] = s.lev[blk][l];
     if (tid < 16) {
         const int k = tid;
-        const int ip = best_mode == JMH_I4MB ? sc->ipred[k]
-                     : best_mode == JMH_I8MB ? (sc->i8modes >> (4 * (((k >> 3) << 1) + ((k & 3) >> 1)))) & 15 : 2;
+        const int ip = best_mode == JMH_I4MB ? an.ipred(k)
+                     : best_mode == JMH_I8MB ? (an.i8modes() >> (4 * (((k >> 3) << 1) + ((k & 3) >> 1)))) & 15 : 2;
         res->ipred[k] = (int8_t)ip;
         res->mv[k][0] = s.fmv[k][0]; res->mv[k][1] = s.fmv[k][1];
         res->luma_dc[k] = best_mode == JMH_I16MB ? s.dclev[k] : 0;
@@ -401,7 +429,7 @@ __device__ __forceinline__ void final_mb(const TickArgs &t, FinS<pel> &s, int m,
     const pel *refY = spl<pel>(d.refY);
     const int W = d.W, H = d.H, maxv = sizeof(pel) == 1 ? 255 : d.maxv;
     auto mc = [=](int X, int Y) { return qpel_direct<pel, OCC == 8>(refY, W, H, X, Y, maxv); };
-    final_core<OCC, pel, T8, NTH>(d, s, mbx, mby, tid, mc);
+    final_core<OCC, pel, T8, NTH>(d, s, mbx, mby, tid, mc, ScratchAnalysis<pel>{d.scr + mby * d.mbw + mbx});
     if (t.bprof_fin && tid == 0) {
         t.bprof_fin[3 * hwb] = bt0;
         t.bprof_fin[3 * hwb + 1] = wall_clock64();

@@ -49,9 +49,10 @@ __device__ __forceinline__ void i4_tabrow(int lane, int (&tabr)[2]) {
 // (held by lanes 0..12, fetched with ds_bpermute) and scores it: the horizontal Hadamard of the
 // row in registers, the vertical butterflies across the quad's rows by DPP.  One wave minimum of
 // (cost, mode) keys is JM's strict '<' scan in mode order; then dct_luma on lanes 0..15 of the
-// chosen prediction (at QP'Y = QPY + QpBdOffsetY)
+// chosen prediction (at QP'Y = QPY + QpBdOffsetY).  i4lev: where the levels go (MbScratch::i4lev, or
+// k_mb_flow's level array in LDS)
 template <class pel>
-__device__ __forceinline__ void i4_block(const DevParams &d, IntraS<pel> &s, MbScratch *scr, int w, int bx4, int by4, const int (&tabr)[2],
+__device__ __forceinline__ void i4_block(const DevParams &d, IntraS<pel> &s, int16_t (*i4lev)[16], int w, int bx4, int by4, const int (&tabr)[2],
                                          bool avL, bool avT, bool avTL, bool avTR, int qpk, int (&acc)[3],
                                          unsigned long long *pst = nullptr) {   // debug: sub-phase stamps [52..57]
 #define I4ST(k, v) do { if (pst) { asm volatile("" ::"v"(v)); if (__lane_id() == 0) pst[k] = wall_clock64(); } } while (0)
@@ -143,7 +144,7 @@ __device__ __forceinline__ void i4_block(const DevParams &d, IntraS<pel> &s, MbS
     I4ST(56, dq);
     const int rc = quad_inv4x4(dq, l, pp, d.maxv);
     if (lane < 16) {
-        scr->i4lev[blk][l] = (int16_t)lev;
+        i4lev[blk][l] = (int16_t)lev;
         s.rec[(by + (l >> 2)) * 16 + bx + (l & 3)] = (pel)rc;
         if (l == 0) s.ipred_cur[blk] = (int8_t)best;
     }

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(64) void k_i4_bench(DevParams d, const uint8_t *src
             const int bx4 = 2 * ((blk >> 2) & 1) + (blk & 1), by4 = 2 * (blk >> 3) + ((blk >> 1) & 1);
             // stamps (argument 3): i4_block's sub-phase clocks [52..57] of block blk, last repeat of WG 0
             unsigned long long *pst = stamps && b == 0 && r == reps - 1 ? stamps + 6 * blk - 52 : nullptr;
-            i4_block(d, s, sc, 0, bx4, by4, tabr, true, true, true, true, qpk, acc, pst);
+            i4_block(d, s, sc->i4lev, 0, bx4, by4, tabr, true, true, true, true, qpk, acc, pst);
         }
         const unsigned long long t1 = __builtin_amdgcn_s_memtime();
         tot += t1 - t0;
