@@ -63,7 +63,7 @@ struct MeS {
         int16_t h1[WIN_DIM_MAX * WST];        // unclipped vertical 6-tap intermediates (planes only)
         uint2 sad8[NPK * NTA];                // then: the 8x8 SADs of every thread's positions,
     } hs;                                     //   [k][thread] (16x16 / 16x8 / 8x16 searches)
-    unsigned long long *pst;                  // debug: per-stage stamps (thread 0), null when off
+    gptr<unsigned long long> pst;             // debug: per-stage stamps (thread 0), null when off
     int pn;
     alignas(8) IntraS<uint8_t> in;            // the MB's intra decisions, run by waves 6 and 7 (8-aligned: its
                                               //   members' 64-bit LDS accesses stay aligned)
@@ -699,8 +699,13 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, SC *scr, int16
     const bool prof = prof_mb_here(d, mbx, mby);
     PSTAMP(0);
     if (tid == 0) { s.pst = prof ? d.prof + 20 : nullptr; s.pn = 0; }
-    if (tid < 256) { if (!pre) s.in.org[tid] = s.org[tid] = d.orgY[(pix_y + (tid >> 4)) * W + pix_x + (tid & 15)]; }
-    else if (tid >= 384 && tid < 394) { load_border(d, s.bd, tid - 384, mbx, mby); load_border(d, s.in.bd, tid - 384, mbx, mby); }
+    // (k_mb_flow, pre: the intra neighbourhood's loads go out with the border cells', one round trip
+    // for both; the tick kernels keep them behind the window load)
+    if (tid < 256) {
+        if (!pre) s.in.org[tid] = s.org[tid] = d.orgY[(pix_y + (tid >> 4)) * W + pix_x + (tid & 15)];
+        else if (tid >= 128 && tid < 199) load_intra_nb_batch(d, s.in.nb, tid - 128, mbx, mby);
+    }
+    else if (tid >= 384 && tid < 394) load_border(d, s.bd, tid - 384, mbx, mby, &s.in.bd);
     else if (!pre && tid >= 472 && tid < 478) s.in.part[(tid - 472) / 3][(tid - 472) % 3] = 0;
     else if (!pre && tid >= 480 && tid < 512) s.motion_cost[(tid - 480) >> 2][tid & 3] = 0;
     // the MB's Intra4x4 decision (10 diagonal steps, then the results) runs on waves 6 and 7
@@ -714,14 +719,16 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, SC *scr, int16
     {
         // SetupFastFullPelSearch: centre = 16x16 MVP / 4 (trunc), clamped to +-SR; the window
         // load starts right away (its centre depends only on the border cells).  One LDS dword
-        // per task: two aligned global dwords + v_alignbyte inside the picture, clamped bytes
-        // at its edges; columns >= wdim are zero.
+        // per task: two aligned global dwords + v_alignbyte inside the picture; at its edges
+        // the clamped samples picked from the same two dwords; columns >= wdim are zero.
         __syncthreads();
         set_mvp(NbBorder{s.bd}, 0, 0, 16, 16, pcx, pcy);
         scx = iclip(-sr, sr, pcx / 4); scy = iclip(-sr, sr, pcy / 4);
         const int X0 = pix_x + scx - sr - WM, Y0 = pix_y + scy - sr - WM;
         constexpr int ND4 = WST / 4, NWT = (WIN_DIM_MAX * ND4 + NTA - 1) / NTA;
-        // all global loads first (interior dwords; edge tasks fall back to clamped bytes below)
+        // all global loads first: the aligned dwords at and after the task's first sample, clamped
+        // into the row.  An edge task's samples, clamped to columns 0 / W - 1, lie in the first one
+        // (columns 0..2, or W-3..W-1); a task cut off at wdim reads like an interior one
         uint32_t lo_[NWT], hi_[NWT];
         bool fast[NWT];
 #pragma unroll
@@ -729,9 +736,10 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, SC *scr, int16
             const int task = tid + i * NTA;
             const int y = task / ND4, j = task - y * ND4, x0 = X0 + 4 * j;
             fast[i] = task < wdim * ND4 && 4 * j + 3 < wdim && x0 >= 0 && x0 + 3 < W;
-            const uint32_t *p = reinterpret_cast<const uint32_t *>(d.refY + iclip(0, d.H - 1, Y0 + y) * W + (fast[i] ? (x0 & ~3) : 0));
+            const int bx = iclip(0, W - 4, x0 & ~3);
+            const gptr<const uint32_t> p = reinterpret_cast<gptr<const uint32_t>>(d.refY + iclip(0, d.H - 1, Y0 + y) * W + bx);
             lo_[i] = p[0];
-            hi_[i] = (fast[i] && (x0 & 3)) ? p[1] : 0u;
+            hi_[i] = ((x0 & 3) && bx + 4 < W) ? p[1] : 0u;
         }
 #pragma unroll
         for (int i = 0; i < NWT; i++) {
@@ -741,17 +749,19 @@ __device__ __forceinline__ void me_mb(const DevParams &d, MeS &s, SC *scr, int16
             uint32_t v;
             if (fast[i]) v = __builtin_amdgcn_alignbyte(hi_[i], lo_[i], x0 & 3);
             else {
-                const uint8_t *row = d.refY + iclip(0, d.H - 1, Y0 + y) * W;
+                const int bx = iclip(0, W - 4, x0 & ~3);
                 v = 0;
 #pragma unroll
-                for (int q = 0; q < 4; q++)
-                    if (4 * j + q < wdim) v |= (uint32_t)row[iclip(0, W - 1, x0 + q)] << (8 * q);
+                for (int q = 0; q < 4; q++) {
+                    const int c = iclip(0, W - 1, x0 + q) - bx;   // in [0, 7]; >= 4 only inside the picture, x0 & 3 != 0
+                    if (4 * j + q < wdim) v |= (((c < 4 ? lo_[i] : hi_[i]) >> (8 * (c & 3))) & 255u) << (8 * q);
+                }
             }
             *reinterpret_cast<uint32_t *>(G + y * WST + 4 * j) = v;
         }
         if (tid < 32) G[wdim * WST + tid] = 0;
         // intra neighbourhood (first read in intra slot 0, after the next barriers)
-        if (tid >= 128 && tid < 199) load_intra_nb(d, s.in.nb, tid - 128, mbx, mby);
+        if (!pre && tid >= 128 && tid < 199) load_intra_nb(d, s.in.nb, tid - 128, mbx, mby);
     }
     __syncthreads();
     PSTAMP(1);
@@ -887,7 +897,7 @@ __device__ __forceinline__ void intra_role(const DevParams &d, IntraS<pel> &s, S
     const bool prof = act && prof_mb_here(d, mbx, mby);
     PSTAMP(12);
     if (act) {
-        const pel *orgY = spl<pel>(d.orgY);
+        const gptr<const pel> orgY = spl<pel>(d.orgY);
         s.org[tid] = orgY[(pix_y + (tid >> 4)) * W + pix_x + (tid & 15)];
         s.org[tid + 128] = orgY[(pix_y + 8 + (tid >> 4)) * W + pix_x + (tid & 15)];
         load_orgc(d, s.nb, tid, mbx, mby);
@@ -949,7 +959,7 @@ __device__ __forceinline__ void intra_slot(const DevParams &d, IntraS<uint8_t> &
         const int by4 = by_lo + w, bx4 = k - 2 * by4;
         if (by4 <= 3 && bx4 >= 0 && bx4 <= 3) {   // the wave's running cost / cbp / block mask live in LDS
             int acc[3] = {s.part[w][0], s.part[w][1], s.part[w][2]};
-            unsigned long long *pst = (k == 4 && w == 0 && d.prof && d.prof_mb == mby * d.mbw + mbx) ? d.prof : nullptr;   // debug stamps
+            const gptr<unsigned long long> pst = (k == 4 && w == 0 && d.prof && d.prof_mb == mby * d.mbw + mbx) ? d.prof : nullptr;   // debug stamps
             i4_block(d, s, i4lev, w, bx4, by4, tabr, avL, avT, avTL, avTR, qpk, acc, pst);
             if (lane == 0) { s.part[w][0] = acc[0]; s.part[w][1] = acc[1]; s.part[w][2] = acc[2]; }
         }
@@ -1078,15 +1088,11 @@ __device__ __forceinline__ DevParams flow_params(const FlowArgs &f, const PicPar
     d.slice_mbs = f.slice_mbs;
     d.maxv = 255; d.qpbd = 0;
     const int ls = W * H, lc = ls >> 2;
-    d.orgY = q.org; d.orgU = q.org + ls; d.orgV = q.org + ls + lc;
-    d.refY = q.ref; d.refU = q.ref + ls; d.refV = q.ref + ls + lc;
-    d.recY = q.rec; d.recU = q.rec + ls; d.recV = q.rec + ls + lc;
-    d.dbkY = q.dbk; d.dbkU = q.dbk ? q.dbk + ls : nullptr; d.dbkV = q.dbk ? q.dbk + ls + lc : nullptr;
+    set_pic_pointers(d, q, ls, lc);
     d.lf_disable = q.lf_disable; d.lf_offA = q.lf_offA; d.lf_offB = q.lf_offB;
-    d.mv = q.mv; d.refidx = q.refidx; d.ipred = q.ipred; d.res = q.res;
     d.scr = nullptr;                                     // (the analysis' results stay in LDS: FlowAnalysis)
     d.tmv = nullptr; d.tref = nullptr; d.ordtab = f.ordtab;
-    d.prof = f.prof; d.prof_mb = f.prof_mb;
+    d.prof = to_global(f.prof); d.prof_mb = f.prof_mb;
     d.slice_type = q.slice_type; d.qp = q.qp; d.lambda_motion = q.lambda_motion;
     d.lambda_mode = __builtin_amdgcn_readfirstlane(q.lambda_mode);   // an SGPR: a VGPR held across me_mb spilled
     d.cqp_off = q.cqp_off; d.qsel = q.qsel; d.diag = q.diag; d.y_min = q.y_min;
@@ -1135,6 +1141,7 @@ struct PlaneMC {
 // reconstruction in the MB's IntraS, the Intra4x4 levels in the final's own level array, the rest
 // in the MbCarry.  (No Intra8x8 in the dataflow path: T8 = false.)
 struct FlowAnalysis {
+    static constexpr bool in_lds = true;
     const MeS &me;
     const IntraS<uint8_t> &in;
     const MbCarry &c;

@@ -367,19 +367,22 @@ __device__ __forceinline__ int border_cell(int xN, int yN) {   // -1: inside the
     if (xN < 0) return yN > 15 ? -1 : 6 + (yN >> 2);
     return -1;
 }
-// prefetch by threads t < 10 of the workgroup
-__device__ __forceinline__ void load_border(const DevParams &d, Border &b, int t, int mbx, int mby) {
+// prefetch by threads t < 10 of the workgroup: one round trip (the cell's three loads are
+// independent global loads; its MV pair is one aligned dword).  b2: a second copy of the cell
+__device__ __forceinline__ void load_border(const DevParams &d, Border &b, int t, int mbx, int mby, Border *b2 = nullptr) {
     const int W4 = d.W >> 2;
     int by4 = t < 6 ? -1 : t - 6, bx4 = t < 6 ? t - 1 : -1;
     const MbAvail m = mb_avail(d, mbx, mby);
     bool av = by4 < 0 ? (bx4 < 0 ? m.TL : bx4 > 3 ? m.TR : m.T) : m.L;
-    int ref = -2, mx = 0, my = 0, ipm = -1;
+    int ref = -2, ipm = -1;
+    uint32_t mvw = 0;                      // mv[2a] | mv[2a + 1] << 16
     if (av) {
         int a = (4 * mby + by4) * W4 + 4 * mbx + bx4;
-        ref = d.refidx[a]; mx = d.mv[2 * a]; my = d.mv[2 * a + 1]; ipm = d.ipred[a];
+        ref = d.refidx[a]; mvw = *reinterpret_cast<gptr<const uint32_t>>(d.mv + 2 * a); ipm = d.ipred[a];
         if (d.cip && ref >= 0) ipm = -1;   // UseConstrainedIntraPred: an inter neighbour sets dcPredModePredictedFlag
     }
-    b.ref[t] = (int8_t)ref; b.mv[t][0] = (int16_t)mx; b.mv[t][1] = (int16_t)my; b.ipm[t] = (int8_t)ipm;
+    b.ref[t] = (int8_t)ref; b.mv[t][0] = (int16_t)(mvw & 0xFFFF); b.mv[t][1] = (int16_t)(mvw >> 16); b.ipm[t] = (int8_t)ipm;
+    if (b2) { b2->ref[t] = (int8_t)ref; b2->mv[t][0] = (int16_t)(mvw & 0xFFFF); b2->mv[t][1] = (int16_t)(mvw >> 16); b2->ipm[t] = (int8_t)ipm; }
 }
 // neighbour view with only border cells (16x16 MVP, skip MV)
 struct NbBorder {

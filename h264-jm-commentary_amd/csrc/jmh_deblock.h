@@ -75,19 +75,19 @@ struct DbkS {
     pel dy[20][20];                      // luma, rows / columns -4..15 -> [r + 4][c + 4]
     pel dc2[2][12][12];                  // chroma, rows / columns -4..7
     int8_t bs[2][4][4];                  // boundary strength [dir][edge][segment]
-    int16_t nmv[2][4][2];                // deblock_prefetch: the left / top neighbour's MV of each
+    int16_t nmv[2][4][2];                // deblock_stage: the left / top neighbour's MV of each
     int32_t nbits[2];                    //   edge segment's 4x4 block, its cbp_blk bits and intra flag
     int8_t nintra[2];
 };
 
 // DeblockMb's inputs from outside the macroblock -- the left and top neighbours' filtered samples
 // (4 rows / columns, luma and chroma) and the mb_type / cbp_blk / MVs its boundary strengths read
-// -- into LDS, NTH threads.  Final from the moment the MB's dependencies are done: only the MB
-// itself, its left / top neighbours and the top-right one (done before it) write those samples, so
-// the caller issues these loads early (final_core: with its own inputs) and deblock_mb<PRE> uses them.
+// -- on NTH threads.  Final from the moment the MB's dependencies are done: only the MB itself, its
+// left / top neighbours and the top-right one (done before it) write those samples, so the caller
+// issues these loads early (final_core: with its own inputs) and deblock_mb<PRE> uses them.
 template <class pel, int NTH>
 __device__ __forceinline__ void deblock_prefetch(const DevParams &d, DbkS<pel> &s, int mbx, int mby, int tid) {
-    const pel *dbkY = spl<pel>(d.dbkY), *dbkU = spl<pel>(d.dbkU), *dbkV = spl<pel>(d.dbkV);
+    const gptr<const pel> dbkY = spl<pel>(d.dbkY), dbkU = spl<pel>(d.dbkU), dbkV = spl<pel>(d.dbkV);
     const int pix_x = 16 * mbx, pix_y = 16 * mby, W = d.W, Wc = d.Wc;
     const bool dbL = mbx > 0, dbT = mby > 0;
     for (int i = tid; i < 256 + 16; i += NTH) {
@@ -104,7 +104,7 @@ __device__ __forceinline__ void deblock_prefetch(const DevParams &d, DbkS<pel> &
             const int j = i - 256, dir = j >> 3, k = j & 7;
             const bool av = dir == 0 ? dbL : dbT;
             if (av) {
-                const jmh_mb_result *rp = d.res + (dir == 0 ? mby * d.mbw + mbx - 1 : (mby - 1) * d.mbw + mbx);
+                const gptr<const jmh_mb_result> rp = d.res + (dir == 0 ? mby * d.mbw + mbx - 1 : (mby - 1) * d.mbw + mbx);
                 if (k < 4) {
                     const int bp = dir == 0 ? k * 4 + 3 : 12 + k;
                     s.nmv[dir][k][0] = rp->mv[bp][0];
@@ -113,6 +113,84 @@ __device__ __forceinline__ void deblock_prefetch(const DevParams &d, DbkS<pel> &
                     s.nbits[dir] = rp->cbp_blk;
                 } else if (k == 5) {
                     const int t = rp->mb_type;
+                    s.nintra[dir] = t == JMH_I4MB || t == JMH_I16MB || t == JMH_I8MB;
+                }
+            }
+        }
+    }
+}
+// The same in two halves, for k_mb_flow: deblock_fetch issues a thread's loads and deblock_stage
+// writes the values into LDS, so the caller can put its own work between them and no wave waits
+// for the loads before that work.  One value per thread and step, and one load instruction for all
+// of them: the aligned word that holds the sample (a plane is an allocation of its own, whole words
+// long), or one aligned word of the neighbour's jmh_mb_result.
+// dbk_byte: the byte offset in its aligned word of the sample in column c of a plane row (rows start
+// on a word: W is a multiple of 16, a macroblock's chroma 8 samples wide)
+template <class pel> __device__ __forceinline__ unsigned dbk_byte(int c) { return ((unsigned)sizeof(pel) * (unsigned)c) & 3u; }
+template <int NTH> struct DbkFetch { uint32_t v[(256 + 16 + NTH - 1) / NTH]; };
+static_assert(offsetof(jmh_mb_result, mv) % 4 == 0 && offsetof(jmh_mb_result, cbp_blk) % 4 == 0 && offsetof(jmh_mb_result, mb_type) == 0 &&
+              sizeof(jmh_mb_result) % 4 == 0, "deblock_fetch reads the neighbour's results by aligned words");
+template <class pel, int NTH>
+__device__ __forceinline__ DbkFetch<NTH> deblock_fetch(const DevParams &d, int mbx, int mby, int tid) {
+    const gptr<const pel> dbkY = spl<pel>(d.dbkY), dbkU = spl<pel>(d.dbkU), dbkV = spl<pel>(d.dbkV);
+    const int pix_x = 16 * mbx, pix_y = 16 * mby, W = d.W, Wc = d.Wc;
+    const bool dbL = mbx > 0, dbT = mby > 0;
+    DbkFetch<NTH> f;
+#pragma unroll
+    for (int n = 0; n * NTH < 256 + 16; n++) {
+        const int i = tid + n * NTH;
+        gptr<const uint8_t> p = nullptr;                 // the value's byte address (null: none)
+        if (i < 128) {                                   // luma: rows -4..-1 (i < 64), columns -4..-1
+            const bool top = i < 64;
+            const int a = i & 63, r = top ? (a >> 4) - 4 : a >> 2, c = top ? a & 15 : (a & 3) - 4;
+            if (top ? dbT : dbL) p = reinterpret_cast<gptr<const uint8_t>>(dbkY + (pix_y + r) * W + pix_x + c);
+        } else if (i < 256) {                            // chroma: per plane rows -4..-1, columns -4..-1
+            const int j = i - 128, pl = j >> 6, a = j & 63;
+            const bool top = a < 32;
+            const int b = a & 31, r = top ? (b >> 3) - 4 : b >> 2, c = top ? b & 7 : (b & 3) - 4;
+            if (top ? dbT : dbL) p = reinterpret_cast<gptr<const uint8_t>>((pl ? dbkV : dbkU) + ((pix_y >> 1) + r) * Wc + (pix_x >> 1) + c);
+        } else if (i < 256 + 16) {                       // the neighbours' results (bS, 8.7.2.1)
+            const int j = i - 256, dir = j >> 3, k = j & 7;
+            if ((dir == 0 ? dbL : dbT) && k < 6) {
+                const gptr<const jmh_mb_result> rp = d.res + (dir == 0 ? mby * d.mbw + mbx - 1 : (mby - 1) * d.mbw + mbx);
+                // k < 4: the MV pair of the edge segment's 4x4 block; 4: cbp_blk; 5: mb_type (| cbp << 16)
+                const int bp = dir == 0 ? k * 4 + 3 : 12 + k;
+                const int off = k < 4 ? (int)offsetof(jmh_mb_result, mv) + 4 * bp : k == 4 ? (int)offsetof(jmh_mb_result, cbp_blk) : 0;
+                p = reinterpret_cast<gptr<const uint8_t>>(rp) + off;
+            }
+        }
+        // the word as loaded: deblock_stage takes the sample out of it (dbk_byte), so that nothing here
+        // waits for the load
+        f.v[n] = p ? *reinterpret_cast<gptr<const uint32_t>>(p - ((unsigned)(uintptr_t)p & 3u)) : 0u;
+    }
+    return f;
+}
+template <class pel, int NTH>
+__device__ __forceinline__ void deblock_stage(DbkS<pel> &s, const DbkFetch<NTH> &f, int mbx, int mby, int tid) {
+    const bool dbL = mbx > 0, dbT = mby > 0;
+#pragma unroll
+    for (int n = 0; n * NTH < 256 + 16; n++) {
+        const int i = tid + n * NTH;
+        const uint32_t v = f.v[n];
+        if (i < 128) {
+            const bool top = i < 64;
+            const int a = i & 63, r = top ? (a >> 4) - 4 : a >> 2, c = top ? a & 15 : (a & 3) - 4;
+            s.dy[r + 4][c + 4] = (pel)(v >> (8 * dbk_byte<pel>(c)));
+        } else if (i < 256) {
+            const int j = i - 128, pl = j >> 6, a = j & 63;
+            const bool top = a < 32;
+            const int b = a & 31, r = top ? (b >> 3) - 4 : b >> 2, c = top ? b & 7 : (b & 3) - 4;
+            s.dc2[pl][r + 4][c + 4] = (pel)(v >> (8 * dbk_byte<pel>(c)));
+        } else if (i < 256 + 16) {
+            const int j = i - 256, dir = j >> 3, k = j & 7;
+            if (dir == 0 ? dbL : dbT) {
+                if (k < 4) {
+                    s.nmv[dir][k][0] = (int16_t)(v & 0xFFFF);
+                    s.nmv[dir][k][1] = (int16_t)(v >> 16);
+                } else if (k == 4) {
+                    s.nbits[dir] = (int32_t)v;
+                } else if (k == 5) {
+                    const int t = (int16_t)(v & 0xFFFF);
                     s.nintra[dir] = t == JMH_I4MB || t == JMH_I16MB || t == JMH_I8MB;
                 }
             }
@@ -128,7 +206,7 @@ __device__ __forceinline__ void deblock_prefetch(const DevParams &d, DbkS<pel> &
 template <class pel, int NTH = NT, bool PRE = false>
 __device__ __forceinline__ void deblock_mb(const DevParams &d, DbkS<pel> &s, const pel *rec, const pel (*cfin)[64], const int16_t (*fmv)[2],
                                            bool is_intra, int cbp_blk, bool t8flag, int qpy, int qpcy, int mbx, int mby, int tid) {
-    pel *dbkY = spl<pel>(d.dbkY), *dbkU = spl<pel>(d.dbkU), *dbkV = spl<pel>(d.dbkV);
+    const gptr<pel> dbkY = spl<pel>(d.dbkY), dbkU = spl<pel>(d.dbkU), dbkV = spl<pel>(d.dbkV);
     const int pix_x = 16 * mbx, pix_y = 16 * mby, W = d.W, Wc = d.Wc, maxv = d.maxv;
     // deblocking filters across slice edges (disable_deblocking_filter_idc 0): picture edges only
     const bool dbL = mbx > 0, dbT = mby > 0;
@@ -141,7 +219,7 @@ __device__ __forceinline__ void deblock_mb(const DevParams &d, DbkS<pel> &s, con
                 int v = 0;
                 if (r >= 0 && c >= 0) v = rec[16 * r + c];
                 else if ((r < 0) != (c < 0)) {
-                    if (PRE) continue;                   // deblock_prefetch loaded the borders
+                    if (PRE) continue;                   // deblock_stage wrote the borders
                     if ((r < 0 && dbT) || (c < 0 && dbL)) v = dbkY[(pix_y + r) * W + pix_x + c];
                 }
                 s.dy[r + 4][c + 4] = (pel)v;
@@ -174,7 +252,7 @@ __device__ __forceinline__ void deblock_mb(const DevParams &d, DbkS<pel> &s, con
                     pmx = s.nmv[dir][i][0]; pmy = s.nmv[dir][i][1];
                 } else if (mb_edge) {
                     const int nx = dir == 0 ? mbx - 1 : mbx, ny = dir == 0 ? mby : mby - 1;
-                    const jmh_mb_result *rp = d.res + ny * d.mbw + nx;
+                    const gptr<const jmh_mb_result> rp = d.res + ny * d.mbw + nx;
                     intra_p = rp->mb_type == JMH_I4MB || rp->mb_type == JMH_I16MB || rp->mb_type == JMH_I8MB;
                     pcoef = (rp->cbp_blk >> bp) & 1;
                     pref = intra_p ? -1 : 0;

@@ -86,6 +86,25 @@ struct RdoPic {
 // byte offset of the RdoPic in a picture's MbScratch allocation (16-aligned)
 __host__ __device__ __forceinline__ size_t rdo_pic_offset(size_t nmb) { return (nmb * sizeof(MbScratch) + 15) & ~(size_t)15; }
 
+// A pointer to global memory (HBM) with the address space in its type: an access through it is a
+// global_load / global_store whatever the compiler can prove about where the pointer came from.  A
+// generic pointer loaded from memory (k_mb_flow's PicParams come from a device table) compiles to
+// flat_* accesses, which count on the LDS counter as well and are ordered against every ds_write.
+// Only tick_params and flow_params make one from a generic pointer (to_global); a pointer into LDS
+// does not convert, so it cannot be read as global by mistake (the other way is implicit).
+// The type is in force in k_mb_flow's translation unit (JMH_FLOW_TU), which compiles every helper
+// the dataflow path shares with the tick kernels.  In the tick kernels' own units the alias is a
+// generic pointer: theirs come from kernel arguments, which the compiler knows to be global (no
+// flat_* there), and with the typed form their register allocation moved (a few spilled SGPRs more
+// or less per kernel, 4 B more scratch in k_mb_intra) for nothing.
+#if defined(__HIP_DEVICE_COMPILE__) && defined(JMH_FLOW_TU)
+template <class T> using gptr = __attribute__((address_space(1))) T *;
+#define JMH_TYPED_GPTR 1
+#else
+template <class T> using gptr = T *;
+#endif
+template <class T> __host__ __device__ __forceinline__ gptr<T> to_global(T *p) { return (gptr<T>)p; }
+
 struct DevParams {
     int W, H, Wc, Hc, mbw, mbh;
     int sr, side, npos;
@@ -101,20 +120,20 @@ struct DevParams {
     int maxv, qpbd;             // (1 << bit depth) - 1 (Clip1), QpBdOffsetY = QpBdOffsetC = 6 (bit depth - 8)
     // plane pointers are byte addresses of uint8_t (bit depth 8) or uint16_t (9 / 10) samples:
     // the kernels templated on the sample type cast them (spl<pel>)
-    const uint8_t *orgY, *orgU, *orgV;
-    const uint8_t *refY, *refU, *refV;
-    uint8_t *recY, *recU, *recV;
-    uint8_t *dbkY, *dbkU, *dbkV;   // deblocked reconstruction (null: no deblocking on the device)
+    gptr<const uint8_t> orgY, orgU, orgV;
+    gptr<const uint8_t> refY, refU, refV;
+    gptr<uint8_t> recY, recU, recV;
+    gptr<uint8_t> dbkY, dbkU, dbkV;   // deblocked reconstruction (null: no deblocking on the device)
     int lf_disable, lf_offA, lf_offB;   // disable_deblocking_filter_idc, FilterOffsetA/B (= 2 x div2)
-    int16_t *mv;
-    int8_t *refidx;
-    int8_t *ipred;
+    gptr<int16_t> mv;
+    gptr<int8_t> refidx;
+    gptr<int8_t> ipred;
     const int16_t *tmv;         // EPZS temporal predictors: the previous picture's MVs / ref_idx
     const int8_t *tref;         //   (null: no previous picture)
     const uint32_t *ordtab;     // FFS: JM order keys of every thread's positions (ordtab_fill)
-    jmh_mb_result *res;
-    MbScratch *scr;
-    unsigned long long *prof;   // debug phase timestamps (null: off)
+    gptr<jmh_mb_result> res;
+    MbScratch *scr;             // (tick kernels only, like tmv / tref / rp: generic, from kernel arguments)
+    gptr<unsigned long long> prof;   // debug phase timestamps (null: off)
     int prof_mb;
     int slice_type, qp, lambda_mode, lambda_motion, cqp_off;
     int qsel;                   // quantisation rounding selector of this slice (q_round, jmh_common.h)
@@ -276,6 +295,17 @@ __device__ __forceinline__ int tick_entry(const TickArgs &t, int idx) {
     while (e + 1 < t.npic && t.pre[e + 1] <= idx) e++;
     return e;
 }
+// the picture's planes, side arrays and results as global pointers (ls / lc: bytes of a luma / chroma
+// plane): the one place where DevParams' typed pointers are made
+__device__ __forceinline__ void set_pic_pointers(DevParams &d, const PicParams &q, int ls, int lc) {
+    const gptr<const uint8_t> org = to_global(q.org), ref = to_global(q.ref);
+    const gptr<uint8_t> rec = to_global(q.rec), dbk = to_global(q.dbk);
+    d.orgY = org; d.orgU = org + ls; d.orgV = org + ls + lc;
+    d.refY = ref; d.refU = ref + ls; d.refV = ref + ls + lc;
+    d.recY = rec; d.recU = rec + ls; d.recV = rec + ls + lc;
+    d.dbkY = dbk; d.dbkU = dbk ? dbk + ls : nullptr; d.dbkV = dbk ? dbk + ls + lc : nullptr;
+    d.mv = to_global(q.mv); d.refidx = to_global(q.refidx); d.ipred = to_global(q.ipred); d.res = to_global(q.res);
+}
 __device__ __forceinline__ bool inter_on(int isr, int mode) { return (isr >> mode) & 1; }
 __device__ __forceinline__ DevParams tick_params(const TickArgs &t, int e) {
     DevParams d;
@@ -293,14 +323,11 @@ __device__ __forceinline__ DevParams tick_params(const TickArgs &t, int e) {
     d.slice_mbs = t.slice_mbs;
     d.maxv = (1 << t.bd) - 1; d.qpbd = 6 * (t.bd - 8);
     const int ps = t.bd > 8 ? 2 : 1, ls = t.W * t.H * ps, lc = ls >> 2;
-    d.orgY = q.org; d.orgU = q.org + ls; d.orgV = q.org + ls + lc;
-    d.refY = q.ref; d.refU = q.ref + ls; d.refV = q.ref + ls + lc;
-    d.recY = q.rec; d.recU = q.rec + ls; d.recV = q.rec + ls + lc;
-    d.dbkY = q.dbk; d.dbkU = q.dbk ? q.dbk + ls : nullptr; d.dbkV = q.dbk ? q.dbk + ls + lc : nullptr;
+    set_pic_pointers(d, q, ls, lc);
     d.lf_disable = q.lf_disable; d.lf_offA = q.lf_offA; d.lf_offB = q.lf_offB;
-    d.mv = q.mv; d.refidx = q.refidx; d.ipred = q.ipred; d.res = q.res; d.scr = q.scr;
+    d.scr = q.scr;
     d.tmv = q.tmv; d.tref = q.tref; d.ordtab = t.ordtab;
-    d.prof = e == 0 ? t.prof : nullptr; d.prof_mb = t.prof_mb;
+    d.prof = e == 0 ? to_global(t.prof) : nullptr; d.prof_mb = t.prof_mb;
     d.slice_type = q.slice_type; d.qp = q.qp; d.lambda_mode = q.lambda_mode; d.lambda_motion = q.lambda_motion;
     d.cqp_off = q.cqp_off; d.qsel = q.qsel; d.diag = q.diag; d.y_min = q.y_min;
     d.rdo = t.rdo;
@@ -331,6 +358,11 @@ __device__ __forceinline__ void tick_mb(const TickArgs &t, const DevParams &d, i
     }
 }
 
-// sample-typed view of a DevParams plane pointer (bytes of uint8_t or uint16_t samples)
+// sample-typed view of a DevParams plane pointer (bytes of uint8_t or uint16_t samples), in the
+// pointer's address space; the generic forms serve MbScratch's byte arrays
 template <class pel> __device__ __forceinline__ pel *spl(uint8_t *p) { return reinterpret_cast<pel *>(p); }
 template <class pel> __device__ __forceinline__ const pel *spl(const uint8_t *p) { return reinterpret_cast<const pel *>(p); }
+#ifdef JMH_TYPED_GPTR
+template <class pel> __device__ __forceinline__ gptr<pel> spl(gptr<uint8_t> p) { return (gptr<pel>)p; }
+template <class pel> __device__ __forceinline__ gptr<const pel> spl(gptr<const uint8_t> p) { return (gptr<const pel>)p; }
+#endif

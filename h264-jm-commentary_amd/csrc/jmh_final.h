@@ -47,6 +47,7 @@ struct FinS {
 // in its workgroup's LDS (FlowAnalysis, jmh_analyse.hip).
 template <class pel>
 struct ScratchAnalysis {
+    static constexpr bool in_lds = false;
     const MbScratch *sc;
     __device__ __forceinline__ int motion_cost(int m, int k) const { return sc->motion_cost[m][k]; }
     __device__ __forceinline__ int mv(int m, int k, int c) const { return sc->all_mv[m][k][c]; }
@@ -98,9 +99,9 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     const int slice_p = d.slice_type == JMH_P_SLICE;
     // QPY (deblocking) and QP'Y = QPY + QpBdOffsetY (quantisation); Clip1 to maxv
     const int qpy = d.qp, qp = d.qp + d.qpbd, maxv = d.maxv;
-    const pel *orgY = spl<pel>(d.orgY), *orgU = spl<pel>(d.orgU), *orgV = spl<pel>(d.orgV);
-    const pel *refU = spl<pel>(d.refU), *refV = spl<pel>(d.refV);
-    pel *recY = spl<pel>(d.recY), *recU = spl<pel>(d.recU), *recV = spl<pel>(d.recV);
+    const gptr<const pel> orgY = spl<pel>(d.orgY), orgU = spl<pel>(d.orgU), orgV = spl<pel>(d.orgV);
+    const gptr<const pel> refU = spl<pel>(d.refU), refV = spl<pel>(d.refV);
+    const gptr<pel> recY = spl<pel>(d.recY), recU = spl<pel>(d.recU), recV = spl<pel>(d.recV);
     const MbAvail mav = intra_avail(d, mbx, mby);   // (the intra prediction's neighbours)
     const bool avL = mav.L, avT = mav.T, avTL = mav.TL;
     const bool prof = prof_mb_here(d, mbx, mby);
@@ -113,7 +114,15 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     const pel(*S_ctop)[12] = pnb ? pnb->ctop : s.ctop;
     const pel(*S_cleft)[8] = pnb ? pnb->cleft : s.cleft;
     if (lu && !porg) s.org[tid] = orgY[(pix_y + (tid >> 4)) * W + pix_x + (tid & 15)];
-    if (d.dbkY) deblock_prefetch<pel, NTH>(d, s.db, mbx, mby, tid);   // its latency under the decision and the luma
+    // DeblockMb's inputs: loaded here (their latency under the decision and the luma).  k_mb_flow
+    // holds them in registers until the mode decision is through (LATE), so that no wave waits for
+    // them before it; the tick kernels, at their register limits, put them into LDS at once
+    constexpr bool LATE = AV::in_lds;
+    DbkFetch<NTH> dbf = {};
+    if (d.dbkY) {
+        if constexpr (LATE) dbf = deblock_fetch<pel, NTH>(d, mbx, mby, tid);
+        else deblock_prefetch<pel, NTH>(d, s.db, mbx, mby, tid);
+    }
     if (!pnb && (!W2 || tid >= 256)) {
         const int u = ct;
         if (u < 128) {
@@ -177,7 +186,7 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
             cpredv = chroma_pred_px(S_ctop[cuv] + 1, S_cleft[cuv], S_ctop[cuv][0], avT, avL, c_mode, cxo, cyo, maxv);
         } else {
             // OneComponentChromaPrediction4x4 [J] / 8.4.2.2.2
-            const pel *R = cuv ? refV : refU;
+            const gptr<const pel> R = cuv ? refV : refU;
             const int vx = s.fmv[(cyo >> 1) * 4 + (cxo >> 1)][0], vy = s.fmv[(cyo >> 1) * 4 + (cxo >> 1)][1];
             const int ii = ((pix_x >> 1) + cxo) * 8 + vx, jj = ((pix_y >> 1) + cyo) * 8 + vy;
             const int x0 = iclip(0, Wc - 1, ii >> 3), y0 = iclip(0, d.Hc - 1, jj >> 3);
@@ -187,6 +196,8 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
                       fx * fy * R[y1 * Wc + x1] + 32) >> 6;
         }
     }
+    if constexpr (LATE)
+        if (d.dbkY) deblock_stage<pel, NTH>(s.db, dbf, mbx, mby, tid);   // (behind the reference reads: one wait for both)
     // dct_chroma [J] in three parts: (A) forward transform + AC quantisation per 4x4, (B) the 2x2 DC
     // on two threads, (C) inverse transform + reconstruction.  QPc of qPI = Clip3(-QpBdOffsetC, 51,
     // QPY + chroma_qp_index_offset) (8.5.8, Table 8-15: negative qPI map to themselves), quantised
@@ -373,7 +384,7 @@ __device__ __forceinline__ void final_core(DevParams d, FinS<pel> &s, int mbx, i
     cbp |= cr << 4;
 
     // ======== outputs: jmh_mb_result, reconstruction, picture MV / ref / Intra4x4-mode arrays
-    jmh_mb_result *res = d.res + mby * d.mbw + mbx;
+    const gptr<jmh_mb_result> res = d.res + mby * d.mbw + mbx;
     int mb_type = best_mode;
     if (slice_p && best_mode == 1 && cbp == 0 && s.fmv[0][0] == an.skipx() && s.fmv[0][1] == an.skipy()) mb_type = JMH_PSKIP;
     if (tid == 0) {
@@ -426,7 +437,7 @@ __device__ __forceinline__ void final_mb(const TickArgs &t, FinS<pel> &s, int m,
     const int mby = d.y_min + (m - t.pre[e]), mbx = d.diag - 2 * mby;
     // the 64-VGPR build samples the 6-tap's centre column by column: no spills (the unrolled form
     // spilled 56 B per lane and measured 0.9 % faster, profiles/r7b_c3_serialj_ab.txt)
-    const pel *refY = spl<pel>(d.refY);
+    const pel *refY = spl<pel>(d.refY);       // (generic for qpel_direct: a kernel argument's pointer, known global)
     const int W = d.W, H = d.H, maxv = sizeof(pel) == 1 ? 255 : d.maxv;
     auto mc = [=](int X, int Y) { return qpel_direct<pel, OCC == 8>(refY, W, H, X, Y, maxv); };
     final_core<OCC, pel, T8, NTH>(d, s, mbx, mby, tid, mc, ScratchAnalysis<pel>{d.scr + mby * d.mbw + mbx});

@@ -54,7 +54,7 @@ __device__ __forceinline__ void i4_tabrow(int lane, int (&tabr)[2]) {
 template <class pel>
 __device__ __forceinline__ void i4_block(const DevParams &d, IntraS<pel> &s, int16_t (*i4lev)[16], int w, int bx4, int by4, const int (&tabr)[2],
                                          bool avL, bool avT, bool avTL, bool avTR, int qpk, int (&acc)[3],
-                                         unsigned long long *pst = nullptr) {   // debug: sub-phase stamps [52..57]
+                                         gptr<unsigned long long> pst = nullptr) {   // debug: sub-phase stamps [52..57]
 #define I4ST(k, v) do { if (pst) { asm volatile("" ::"v"(v)); if (__lane_id() == 0) pst[k] = wall_clock64(); } } while (0)
     I4ST(52, bx4);
     const int lane = threadIdx.x & 63, l = lane & 15;

@@ -30,7 +30,7 @@ struct IntraNb {
 // prefetch of the intra neighbourhood by threads t in [0, 96)
 template <class pel>
 __device__ __forceinline__ void load_intra_nb(const DevParams &d, IntraNb<pel> &nb, int t, int mbx, int mby) {
-    const pel *recY = spl<pel>(d.recY), *recU = spl<pel>(d.recU), *recV = spl<pel>(d.recV);
+    const gptr<const pel> recY = spl<pel>(d.recY), recU = spl<pel>(d.recU), recV = spl<pel>(d.recV);
     const int pix_x = 16 * mbx, pix_y = 16 * mby, W = d.W, Wc = d.Wc;
     const MbAvail mav = intra_avail(d, mbx, mby);
     const bool avL = mav.L, avT = mav.T, avTL = mav.TL, avTR = mav.TR;
@@ -49,6 +49,37 @@ __device__ __forceinline__ void load_intra_nb(const DevParams &d, IntraNb<pel> &
         const int i = t - 55, uv = i >> 3, y = i & 7;
         nb.cleft[uv][y] = avL ? (uv ? recV : recU)[((pix_y >> 1) + y) * Wc + (pix_x >> 1) - 1] : 0;
     }
+}
+// the same with one load instruction for all threads (k_mb_flow, after its dependency wait: a wave
+// whose threads take several of the branches above makes one round trip, not one per branch)
+template <class pel>
+__device__ __forceinline__ void load_intra_nb_batch(const DevParams &d, IntraNb<pel> &nb, int t, int mbx, int mby) {
+    const gptr<const pel> recY = spl<pel>(d.recY), recU = spl<pel>(d.recU), recV = spl<pel>(d.recV);
+    const int pix_x = 16 * mbx, pix_y = 16 * mby, W = d.W, Wc = d.Wc;
+    const MbAvail mav = intra_avail(d, mbx, mby);
+    const bool avL = mav.L, avT = mav.T, avTL = mav.TL, avTR = mav.TR;
+    // where the thread's sample is and where it goes, then the load
+    gptr<const pel> src = recY;
+    pel *dst = nullptr;
+    bool av = false;
+    if (t < 21) {                                  // luma row y = -1, x = -1..19
+        const int x = t - 1;
+        av = x < 0 ? avTL : x < 16 ? avT : avTR;
+        src = recY + (pix_y - 1) * W + pix_x + x; dst = &nb.rtop[x + 1];
+    } else if (t < 37) {
+        const int y = t - 21;
+        av = avL;
+        src = recY + (pix_y + y) * W + pix_x - 1; dst = &nb.rleft[y];
+    } else if (t < 55) {                           // chroma rows y = -1, x = -1..7
+        const int i = t - 37, uv = i / 9, x = i - 9 * uv - 1;
+        av = x < 0 ? avTL : avT;
+        src = (uv ? recV : recU) + ((pix_y >> 1) - 1) * Wc + (pix_x >> 1) + x; dst = &nb.ctop[uv][x + 1];
+    } else if (t < 71) {
+        const int i = t - 55, uv = i >> 3, y = i & 7;
+        av = avL;
+        src = (uv ? recV : recU) + ((pix_y >> 1) + y) * Wc + (pix_x >> 1) - 1; dst = &nb.cleft[uv][y];
+    }
+    if (dst) *dst = av ? *src : (pel)0;
 }
 template <class pel>
 __device__ __forceinline__ void load_orgc(const DevParams &d, IntraNb<pel> &nb, int t, int mbx, int mby) {   // t in [0, 128)
