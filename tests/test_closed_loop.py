@@ -1,7 +1,14 @@
 """Closed-loop conformance: the CPU reference encoder's bitstream, decoded by the
-independent spec decoder (oracle/decoder.c), reproduces the encoder's reconstruction byte for
-byte.  This pins every normative piece: CAVLC syntax, MVP, intra prediction, inverse transforms,
-interpolation and the deblocking filter (two independent implementations must agree)."""
+spec decoder (oracle/decoder.c), reproduces the encoder's reconstruction byte for byte.
+
+What two independent implementations pin here: the CAVLC / CABAC syntax (the product's host writer
+against the decoder's parser), MV prediction, intra prediction and neighbour availability, the
+dequantisation (the decoder's own level scaling against the encoder's quantiser loop), chroma
+motion compensation and the deblocking filter.  What is shared and therefore not pinned here:
+decoder.c calls the oracle's jmo_qpel_px for luma interpolation and jmo_inverse4x4 /
+jmo_inverse8x8 for the inverse core transforms, the same functions the encoder reconstructs with;
+those rest on the spec known answers of test_oracle_kat.py.  The synthetic input leaves intra
+modes unchosen; test_directed_census.py closes the same loop on pictures that reach all of them."""
 import subprocess
 import tempfile
 
