@@ -24,6 +24,7 @@
 #include "jmh_cabac.h"
 #include "jmh_cabac_rate.h"
 #include "jmh_ingest.h"
+#include "jmh_nal.h"
 
 // Coded pictures: bytes of output per macroblock that a picture's writer is queued with, unless
 // JMH_CODED_CAP says otherwise.  192 B per MB is about four times the densest picture recorded
@@ -89,6 +90,30 @@ static void ring_drain(EvRing &r, float &sum, int &n) {
 }
 
 
+// NAL units finished on the device (jmhip_nal.h): the buffers of one access unit, a
+// ring entry's or the synchronous seam's
+struct NalBuf {
+    uint8_t *h, *d;                      // pinned / device: heads, where, chunk starts, chunk records, unit places, meta (NalLayout)
+    int ucap, maxch;                     //   the units and chunks they hold
+    uint8_t *out;                        // device: the access unit
+    size_t out_cap;
+};
+// offsets into NalBuf::h / d (each a multiple of 8)
+struct NalLayout {
+    size_t heads, where, cs, ch, uout, meta, bytes;
+    NalLayout(int ucap, int maxch) {
+        auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+        heads = 0;
+        where = up8((size_t)ucap * sizeof(jmh_nal_head));
+        cs = where + (size_t)ucap * 3 * sizeof(int64_t);
+        ch = up8(cs + ((size_t)ucap + 1) * sizeof(int32_t));
+        uout = ch + (size_t)maxch * sizeof(jmn_chunk);
+        meta = uout + (size_t)ucap * 2 * sizeof(int64_t);
+        bytes = meta + JMN_META_WORDS * sizeof(uint64_t);
+    }
+};
+static_assert(sizeof(jmn_chunk) % 8 == 0 && sizeof(jmh_nal_range) == 2 * sizeof(int64_t), "NalLayout");
+
 // one ring entry: everything one picture in flight owns
 struct PicBuf {
     uint8_t *src, *rec, *dbk;            // device: source (jmh_frame_push), recon, deblocked recon
@@ -116,6 +141,8 @@ struct PicBuf {
     jmh_coded_slice *cd_sl;              // pinned (inside cd_h): the caller's descriptors, for the synchronous fallback
     uint8_t *cd_out;                     // device: the picture's output region
     size_t cd_cap;                       //   its bytes
+    int nal_armed;                       // the occupant was armed (jmh_coded_nal_heads): its pop returns the access unit
+    NalBuf nal;                          //   the entry's NAL buffers, on its first armed picture
     // device pictures (jmhip_input.h)
     int dev_fmt;                         // the occupant was pushed from device memory: its format + 1, else 0
     hipEvent_t ev_in;                    //   the caller's stream at the push (created on first use)
@@ -221,6 +248,11 @@ struct jmh_ctx {
     size_t coded_cap = 0;                // coded pictures: bytes of output per macroblock queued with a picture
     std::vector<void *> coded_retired;   //   outgrown output regions: freed with the context
     uint8_t *h_coded_pic = nullptr;      //   pinned: jmh_read_recon / jmh_read_deblocked of a coded picture
+    bool nal_armed = false;              // jmh_coded_nal_heads: the next coded push takes nal_arm
+    std::vector<jmh_nal_head> nal_arm;
+    NalBuf nalw = {};                    // jmh_nal_wrap: its buffers,
+    uint8_t *nalw_pay = nullptr;         //   the payload on the device
+    size_t nalw_pay_cap = 0;
     // device pictures: the I010 clamp counts, a word per ring entry and one for the unit seam (on the
     // first I010 picture), the count of the picture last popped, the last device push
     unsigned long long *d_clamp = nullptr, *h_clamp = nullptr;
@@ -266,9 +298,9 @@ int jmh_device_count(void) {
 }  // extern "C"
 
 static void free_entry(PicBuf &b) {
-    void *dev_bufs[] = {b.src, b.rec, b.dbk, b.mv, b.refidx, b.ipred, b.res, b.scr, b.cab, b.range, b.mbi, b.cd_d, b.cd_out};
+    void *dev_bufs[] = {b.src, b.rec, b.dbk, b.mv, b.refidx, b.ipred, b.res, b.scr, b.cab, b.range, b.mbi, b.cd_d, b.cd_out, b.nal.d, b.nal.out};
     for (void *p : dev_bufs) if (p) (void)hipFree(p);
-    void *host_bufs[] = {b.h_res, b.h_src, b.h_rec, b.h_dbk, b.h_rp, b.cd_h};
+    void *host_bufs[] = {b.h_res, b.h_src, b.h_rec, b.h_dbk, b.h_rp, b.cd_h, b.nal.h};
     for (void *p : host_bufs) if (p) (void)hipHostFree(p);
     hipEvent_t evs[] = {b.ev_src, b.ev_t0, b.ev_done, b.ev_fin, b.ev_rp, b.ev_in};
     for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
@@ -394,6 +426,10 @@ void jmh_destroy(jmh_ctx *c) {
     for (PicBuf &b : c->ring) free_entry(b);
     for (void *p : c->coded_retired) (void)hipFree(p);
     if (c->h_coded_pic) (void)hipHostFree(c->h_coded_pic);
+    if (c->nalw.d) (void)hipFree(c->nalw.d);
+    if (c->nalw.out) (void)hipFree(c->nalw.out);
+    if (c->nalw.h) (void)hipHostFree(c->nalw.h);
+    if (c->nalw_pay) (void)hipFree(c->nalw_pay);
     if (c->d_clamp) (void)hipFree(c->d_clamp);
     if (c->h_clamp) (void)hipHostFree(c->h_clamp);
     if (c->up_h) (void)hipHostFree(c->up_h);
@@ -784,6 +820,44 @@ static int flow_check(jmh_ctx *c) {
     return JMH_OK;
 }
 
+// the NAL buffers for n units over payload_cap bytes of payload and out_want bytes of output; an
+// outgrown device buffer is retired, not freed (as alloc_coded).  The pinned block is free to go: a
+// ring entry's previous occupant has been popped, the seam is synchronous
+static int nal_reserve(jmh_ctx *c, NalBuf &nb, int n, size_t payload_cap, size_t out_want) {
+    const int64_t mc = jmh_nal_max_chunks(n, (int64_t)n * JMH_NAL_HEAD_MAX + (int64_t)payload_cap);
+    if (mc > INT32_MAX) return JMH_E_INVALID_ARG;
+    if (n > nb.ucap || (int)mc > nb.maxch) {
+        const int ucap = std::max(n, nb.ucap), maxch = std::max((int)mc, nb.maxch);
+        const NalLayout N(ucap, maxch);
+        if (nb.d) c->coded_retired.push_back(nb.d);
+        if (nb.h) (void)hipHostFree(nb.h);
+        nb.d = nb.h = nullptr; nb.ucap = nb.maxch = 0;
+        if (hipHostMalloc((void **)&nb.h, N.bytes, hipHostMallocDefault) != hipSuccess) { nb.h = nullptr; return JMH_E_OOM; }
+        if (hipMalloc((void **)&nb.d, N.bytes) != hipSuccess) { nb.d = nullptr; (void)hipHostFree(nb.h); nb.h = nullptr; return JMH_E_OOM; }
+        nb.ucap = ucap; nb.maxch = maxch;
+    }
+    if (out_want > nb.out_cap) {
+        if (nb.out) c->coded_retired.push_back(nb.out);
+        nb.out = nullptr; nb.out_cap = 0;
+        if (hipMalloc((void **)&nb.out, out_want) != hipSuccess) { nb.out = nullptr; return JMH_E_OOM; }
+        nb.out_cap = out_want;
+    }
+    return JMH_OK;
+}
+static jmh_nal_job nal_job(const jmh_ctx *c, const NalBuf &nb, int n, const uint8_t *d_payload, size_t payload_cap, const int64_t *d_where,
+                           const uint64_t *d_wmeta, int64_t bins, bool sum_bins) {
+    const NalLayout N(nb.ucap, nb.maxch);
+    jmh_nal_job j;
+    j.n = n; j.d_heads = (const jmh_nal_head *)(nb.d + N.heads); j.d_payload = d_payload; j.payload_cap = (int64_t)payload_cap;
+    j.d_where = d_where; j.d_wmeta = d_wmeta; j.bins = bins; j.sum_bins = sum_bins; j.bd = c->bd; j.nmb = (int)c->nmb;
+    j.d_cs = (int32_t *)(nb.d + N.cs); j.d_ch = (jmn_chunk *)(nb.d + N.ch); j.maxch = nb.maxch; j.d_uout = (int64_t *)(nb.d + N.uout);
+    j.d_meta = (uint64_t *)(nb.d + N.meta); j.d_out = nb.out; j.out_cap = (int64_t)nb.out_cap;
+    return j;
+}
+// the finished bytes a ring entry is queued with: no escape pattern needs more than
+// half again the payload; the heads as if all of them were escapes; the start codes and header bytes
+static size_t nal_region(size_t payload_cap, int n) { return payload_cap + payload_cap / 2 + (size_t)n * (2 * JMH_NAL_HEAD_MAX + JMN_UNIT_OVERHEAD); }
+
 // A coded picture's last tick (ev_fin recorded): its slice writer and its distortion on the writer's
 // stream, with no host wait between the passes, then where[] and the meta words into pinned memory
 // and the done event.  All of it overlaps the ticks of the pictures still in flight; nothing but
@@ -799,6 +873,14 @@ static int finish_coded(jmh_ctx *c, const Flight &f, PicBuf &b) {
                                : jmh_cavlc_enqueue(&c->cavlc, b.res, b.ev_fin, c->mbw, c->mbh, t8, cip, b.cd_n, &job, &wst);
     if (r) return r;
     if ((r = jmh_plane_ssd(wst, b.src, f.pp.dbk ? b.dbk : b.rec, c->W, c->H, b.cd_cw, b.cd_ch, c->ps, job.d_meta + 2))) return r;
+    if (b.nal_armed) {   // the access unit from the writer's bytes, behind the writer: its where[] and overflow word are read on the device
+        const NalLayout N(b.nal.ucap, b.nal.maxch);
+        HCHK(hipMemcpyAsync(b.nal.d + N.heads, b.nal.h + N.heads, (size_t)b.cd_n * sizeof(jmh_nal_head), hipMemcpyHostToDevice, wst));
+        const jmh_nal_job nj = nal_job(c, b.nal, b.cd_n, b.cd_out, b.cd_cap, (const int64_t *)(b.cd_d + L.where), job.d_meta, 0, c->cfg.symbol_mode != 0);
+        if ((r = jmh_nal_enqueue(wst, &nj))) return r;
+        HCHK(hipMemcpyAsync(b.nal.h + N.uout, b.nal.d + N.uout, (size_t)b.cd_n * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, wst));
+        HCHK(hipMemcpyAsync(b.nal.h + N.meta, b.nal.d + N.meta, JMN_META_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, wst));
+    }
     HCHK(hipMemcpyAsync(b.cd_h + L.where, b.cd_d + L.where, (size_t)b.cd_n * sizeof(jmh_slice_bytes), hipMemcpyDeviceToHost, wst));
     HCHK(hipMemcpyAsync(b.cd_h + L.meta, b.cd_d + L.meta, JMH_WRITER_META_BYTES, hipMemcpyDeviceToHost, wst));
     HCHK(hipEventRecord(b.ev_done, wst));
@@ -1192,6 +1274,8 @@ static int ingest_queue(jmh_ctx *c, const jmh_device_picture *p, uint8_t *dst, i
 
 static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *fp, const CodedPush *cp = nullptr) {
     if (!c || !fp) return JMH_E_INVALID_ARG;
+    const bool armed = c->nal_armed && cp;   // jmh_coded_nal_heads holds for one push, whatever becomes of it
+    c->nal_armed = false;
     int r;
     if (s.dev) { if ((r = check_device_pic(c, s.dev))) return r; }
     else if (!s.y || !s.u || !s.v || s.sy < c->W || s.sc < c->Wc) return JMH_E_INVALID_ARG;
@@ -1202,6 +1286,7 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
         if (cp->cw <= 0 || cp->ch <= 0 || cp->cw > c->W || cp->ch > c->H) return JMH_E_INVALID_ARG;
         descs.resize(c->nmb * 24);
         if ((r = coded_descs(c, *cp, descs.data()))) return r;
+        if (armed && (int)c->nal_arm.size() != cp->n) return JMH_E_INVALID_ARG;
     }
     if ((int)c->popq.size() >= c->depth) return JMH_E_STATE;
     HCHK(hipSetDevice(c->dev));
@@ -1211,6 +1296,7 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
     if (cp) {   // no readback: the source staging only (a device picture: none)
         if (!s.dev && !b.h_src && hipHostMalloc((void **)&b.h_src, c->fsize, hipHostMallocDefault) != hipSuccess) { b.h_src = nullptr; return JMH_E_OOM; }
         if ((r = alloc_coded(c, b))) return r;
+        if (armed && (r = nal_reserve(c, b.nal, cp->n, b.cd_cap, nal_region(b.cd_cap, cp->n)))) return r;
     } else if ((r = alloc_host(c, b, !s.dev))) return r;
     if (s.dev) {
         // the device picture packed and padded where a host picture is uploaded: between ev_t0 and
@@ -1239,7 +1325,9 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
         memcpy(b.cd_h + L.sl, descs.data(), (size_t)cp->n * 24);
         memcpy(b.cd_sl, cp->sl, (size_t)cp->n * sizeof(jmh_coded_slice));
         b.cd_n = cp->n; b.cd_cw = cp->cw; b.cd_ch = cp->ch;
+        if (armed) memcpy(b.nal.h + NalLayout(b.nal.ucap, b.nal.maxch).heads, c->nal_arm.data(), (size_t)cp->n * sizeof(jmh_nal_head));
     }
+    b.nal_armed = armed;
     c->popq.push_back(e);
     return push_picture(c, b.src, e, fp, 1);
 }
@@ -1360,7 +1448,137 @@ static void pop_done(jmh_ctx *c, int e) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, c->ring[e].ev_t0, c->ring[e].ev_done) == hipSuccess) c->timing.total_ms = ms;
 }
+// jmh_nal_wrap: heads, ranges and payload up, the four launches, the units' places and the meta words
+// back, all on the copy stream and waited for.  A total beyond the output region (zero words have no
+// bound in the payload) is known after the scan: the region grows to it and the launches run again
+static int nal_wrap_sync(jmh_ctx *c, int n, const jmh_nal_head *heads, const uint8_t *payload, const jmh_nal_range *win, int64_t nbins,
+                         uint8_t *out, size_t cap, jmh_nal_range *wout, int64_t *total) {
+    if (!c || n <= 0 || !heads || !win || !wout || !total) return JMH_E_INVALID_ARG;
+    int64_t extent = 0;
+    for (int i = 0; i < n; i++) {
+        if (heads[i].nbytes < 0 || heads[i].nbytes > JMH_NAL_HEAD_MAX || win[i].offset < 0 || win[i].nbytes < 0 ||
+            win[i].offset > INT64_MAX / 4 || win[i].nbytes > INT64_MAX / 4)
+            return JMH_E_INVALID_ARG;
+        extent = std::max(extent, win[i].offset + win[i].nbytes);
+    }
+    if (extent > 0 && !payload) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    if ((size_t)extent > c->nalw_pay_cap) {
+        if (c->nalw_pay) c->coded_retired.push_back(c->nalw_pay);
+        c->nalw_pay = nullptr; c->nalw_pay_cap = 0;
+        // (a multiple of 4, as the kernels' dword loads of the payload expect of its region)
+        if (hipMalloc((void **)&c->nalw_pay, ((size_t)extent + 3) & ~(size_t)3) != hipSuccess) { c->nalw_pay = nullptr; return JMH_E_OOM; }
+        c->nalw_pay_cap = (size_t)extent;
+    }
+    NalBuf &nb = c->nalw;
+    int r = nal_reserve(c, nb, n, (size_t)extent, nal_region((size_t)extent, n));
+    if (r) return r;
+    if (extent) HCHK(hipMemcpyAsync(c->nalw_pay, payload, (size_t)extent, hipMemcpyHostToDevice, c->cst));
+    const NalLayout N(nb.ucap, nb.maxch);
+    const uint64_t *meta = (const uint64_t *)(nb.h + N.meta);
+    for (int pass = 0;; pass++) {
+        memcpy(nb.h + N.heads, heads, (size_t)n * sizeof(jmh_nal_head));
+        int64_t *w = (int64_t *)(nb.h + N.where);
+        for (int i = 0; i < n; i++) { w[3 * i] = win[i].offset; w[3 * i + 1] = win[i].nbytes; w[3 * i + 2] = 0; }
+        HCHK(hipMemcpyAsync(nb.d + N.heads, nb.h + N.heads, N.cs - N.heads, hipMemcpyHostToDevice, c->cst));
+        const jmh_nal_job nj = nal_job(c, nb, n, c->nalw_pay, (size_t)extent, (const int64_t *)(nb.d + N.where), nullptr, nbins > 0 ? nbins : 0, false);
+        if ((r = jmh_nal_enqueue(c->cst, &nj))) return r;
+        HCHK(hipMemcpyAsync(nb.h + N.uout, nb.d + N.uout, (size_t)n * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->cst));
+        HCHK(hipMemcpyAsync(nb.h + N.meta, nb.d + N.meta, JMN_META_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, c->cst));
+        HCHK(hipStreamSynchronize(c->cst));
+        if (!(uint32_t)meta[1]) break;
+        if (pass || (int64_t)meta[0] <= (int64_t)nb.out_cap) return JMH_E_STATE;
+        if ((r = nal_reserve(c, nb, n, (size_t)extent, (size_t)meta[0]))) return r;
+    }
+    const int64_t *uo = (const int64_t *)(nb.h + N.uout);
+    for (int i = 0; i < n; i++) { wout[i].offset = uo[2 * i]; wout[i].nbytes = uo[2 * i + 1]; }
+    *total = (int64_t)meta[0];
+    if (*total <= 0 || (size_t)*total > nb.out_cap) return JMH_E_STATE;
+    if (!out || (size_t)*total > cap) return JMH_E_INVALID_ARG;
+    HCHK(hipMemcpyAsync(out, nb.out, (size_t)*total, hipMemcpyDeviceToHost, c->cst));
+    HCHK(hipStreamSynchronize(c->cst));
+    return JMH_OK;
+}
+
+// jmh_frame_pop_coded of an armed picture (ring entry e, waited for): the access unit
+static int pop_coded_nal(jmh_ctx *c, int e, uint8_t *out, size_t cap, jmh_coded_bytes *where, jmh_coded_stats *stats) {
+    PicBuf &b = c->ring[e];
+    const CodedLayout L(c->nmb);
+    const NalLayout N(b.nal.ucap, b.nal.maxch);
+    const uint64_t *meta = (const uint64_t *)(b.cd_h + L.meta), *nmeta = (const uint64_t *)(b.nal.h + N.meta);
+    const bool cabac = c->cfg.symbol_mode != 0;
+    const int n = b.cd_n;
+    const int64_t *w = (const int64_t *)(b.cd_h + L.where);          // the slice data: offset, nbytes, then nbits / nbins
+    const int64_t *uo = (const int64_t *)(b.nal.h + N.uout);         // the NAL units: offset, nbytes
+    std::vector<int64_t> sync_where;
+    std::vector<jmh_nal_range> wo;
+    const bool fallback = (uint32_t)meta[1] != 0 || (uint32_t)nmeta[1] != 0;
+    int r = JMH_OK;
+    int64_t total = 0, payload = 0;
+    if (fallback) {
+        // The writer's bytes or the finished ones exceeded what the picture was queued with: the
+        // synchronous writer into host memory, then the synchronous seam on those bytes
+        const int t8 = c->cfg.transform_8x8_mode, cip = c->cfg.constrained_intra_pred;
+        sync_where.resize((size_t)n * 3);
+        std::vector<uint8_t> tmp(std::max(2 * b.cd_cap, (size_t)1 << 16));
+        const void *d = b.cd_h + L.sl;
+        for (int pass = 0; pass < 2; pass++) {
+            r = cabac ? jmh_cabac_run(&c->cabac, b.res, nullptr, b.ev_done, c->mbw, c->mbh, t8, cip, n, (const jmh_cabac_slice_desc *)d, tmp.data(),
+                                      tmp.size(), (jmh_cabac_slice_bytes *)sync_where.data(), c->cabac_split)
+                      : jmh_cavlc_run(&c->cavlc, b.res, nullptr, b.ev_done, c->mbw, c->mbh, t8, cip, n, (const jmh_slice_desc *)d, tmp.data(),
+                                      tmp.size(), (jmh_slice_bytes *)sync_where.data());
+            payload = sync_where[3 * (n - 1)] + sync_where[3 * (n - 1) + 1];
+            if (r != JMH_E_INVALID_ARG || payload <= (int64_t)tmp.size()) break;
+            tmp.resize((size_t)payload);
+        }
+        if (r) return r;
+        w = sync_where.data();
+        std::vector<jmh_nal_range> wi((size_t)n);
+        wo.resize((size_t)n);
+        int64_t bins = 0;
+        for (int i = 0; i < n; i++) { wi[i].offset = w[3 * i]; wi[i].nbytes = w[3 * i + 1]; if (cabac) bins += w[3 * i + 2]; }
+        r = nal_wrap_sync(c, n, (const jmh_nal_head *)(b.nal.h + N.heads), tmp.data(), wi.data(), bins, out, cap, wo.data(), &total);
+        if (r && r != JMH_E_INVALID_ARG) return r;
+    } else total = (int64_t)nmeta[0];
+    for (int i = 0; i < n; i++) {
+        where[i].offset = fallback ? wo[i].offset : uo[2 * i]; where[i].nbytes = fallback ? wo[i].nbytes : uo[2 * i + 1];
+        where[i].nbits = cabac ? 0 : w[3 * i + 2]; where[i].nbins = cabac ? w[3 * i + 2] : 0;
+    }
+    if (fallback) {
+        if (r) return r;                     // cap below the access unit's bytes: where[] is filled, the picture stays
+        const size_t need = ((size_t)payload * 3 / 2 + c->nmb - 1) / c->nmb;
+        c->coded_cap = std::max(need, std::min(2 * c->coded_cap, (size_t)JMW_MB_MAX_BYTES_ANY));
+    } else {
+        if (total <= 0 || (size_t)total > b.nal.out_cap || where[n - 1].offset + where[n - 1].nbytes != total) return JMH_E_STATE;
+        if (!out || (size_t)total > cap) return JMH_E_INVALID_ARG;
+        HCHK(hipMemcpyAsync(out, b.nal.out, (size_t)total, hipMemcpyDeviceToHost, c->cst));
+        HCHK(hipStreamSynchronize(c->cst));
+    }
+    for (int pl = 0; pl < 3; pl++) stats->ssd[pl] = meta[2 + pl];
+    stats->fallback = fallback; stats->reserved = 0;
+    pop_done(c, e);
+    return JMH_OK;
+}
+
 extern "C" {
+int jmh_nal_geometry(int *tile_bytes, int *chunk_bytes) {
+    if (!tile_bytes || !chunk_bytes) return JMH_E_INVALID_ARG;
+    *tile_bytes = JMN_TILE; *chunk_bytes = JMN_CHUNK;
+    return JMH_OK;
+}
+int jmh_nal_wrap(jmh_ctx *c, int n, const jmh_nal_head *heads, const uint8_t *payload, const jmh_nal_range *where_in, int64_t nbins_total,
+                 uint8_t *out, size_t cap, jmh_nal_range *where_out, int64_t *total) {
+    return nal_wrap_sync(c, n, heads, payload, where_in, nbins_total, out, cap, where_out, total);
+}
+int jmh_coded_nal_heads(jmh_ctx *c, int n, const jmh_nal_head *heads) {
+    if (!c || n <= 0 || n > (int)c->nmb || !heads) return JMH_E_INVALID_ARG;
+    for (int i = 0; i < n; i++)
+        if (heads[i].nbytes < 0 || heads[i].nbytes > JMH_NAL_HEAD_MAX) return JMH_E_INVALID_ARG;
+    c->nal_arm.assign(heads, heads + n);
+    c->nal_armed = true;
+    return JMH_OK;
+}
+
 int jmh_frame_pop(jmh_ctx *c) {
     if (!c) return JMH_E_INVALID_ARG;
     if (c->popq.empty() || c->ring[c->popq.front()].coded) return JMH_E_STATE;   // a coded picture: jmh_frame_pop_coded
@@ -1390,6 +1608,7 @@ int jmh_frame_pop_coded(jmh_ctx *c, uint8_t *out, size_t cap, jmh_coded_bytes *w
     // where[] of either coder: offset, nbytes, then nbits / nbins
     const int64_t *w = (const int64_t *)(b.cd_h + L.where);
     std::vector<int64_t> sync_where;
+    if (b.nal_armed) return pop_coded_nal(c, e, out, cap, where, stats);
     const bool fallback = (uint32_t)meta[1] != 0;
     if (fallback) {
         // A counted size exceeded what the picture was queued with, so its passes wrote nothing: the

@@ -40,6 +40,17 @@ void jm_trailing_bits(jm_bits *b) {
 }
 void jm_bits_align_flush(jm_bits *b) { while (b->nacc) jm_put(b, 0, 1); }
 void jm_bits_append(jm_bits *b, const jm_bits *src) { for (long i = 0; i < src->len; i++) put_byte(b, src->buf[i]); }
+void jm_bits_append_bytes(jm_bits *b, const uint8_t *src, long n) {
+    if (n <= 0) return;
+    if (b->len + n > b->cap) {
+        long cap = b->cap ? b->cap : 4096;
+        while (cap < b->len + n) cap *= 2;
+        b->buf = (uint8_t *)realloc(b->buf, cap);
+        b->cap = cap;
+    }
+    memcpy(b->buf + b->len, src, n);
+    b->len += n;
+}
 
 void jm_write_nal(jm_bits *out, int nal_ref_idc, int nal_type, const jm_bits *rbsp) {
     put_byte(out, 0); put_byte(out, 0); put_byte(out, 0); put_byte(out, 1);

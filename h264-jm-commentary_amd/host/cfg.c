@@ -71,6 +71,7 @@ static const map_entry Map[] = {
     {"DeviceCABACSplit", 0, OFF(device_cabac_split), 0, 65536},
     {"DeviceWriterAsync", 0, OFF(device_writer_async), 0, 1},
     {"DeviceInput", 0, OFF(device_input), 0, 1},
+    {"DeviceNAL", 0, OFF(device_nal), 0, 1},
     {"JMVersion", 0, OFF(jm_version), 8, 99},
     {"QOffsetIntra", 0, OFF(qoff_intra), -1, JMH_QOFFSET_MAX},
     {"QOffsetInter", 0, OFF(qoff_inter), -1, JMH_QOFFSET_MAX},
@@ -198,6 +199,7 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->device_cavlc && inp->jm_call_surface) { snprintf(err, errlen, "DeviceCAVLC=1 replaces the write_one_macroblock loop that JMCallSurface=1 runs (JMCallSurface=0)"); return -1; }
     if (inp->device_writer_async && !inp->device_cavlc && !inp->device_cabac) { snprintf(err, errlen, "DeviceWriterAsync=1 queues the device slice writer behind each picture: it needs DeviceCAVLC=1 (SymbolMode=0) or DeviceCABAC=1 (SymbolMode=1)"); return -1; }
     if (inp->device_writer_async && inp->pipeline_depth == 1) { snprintf(err, errlen, "DeviceWriterAsync=1 runs the writer under the pictures in flight: it needs the pipelined path (PipelineDepth=0 or > 1)"); return -1; }
+    if (inp->device_nal && !inp->device_writer_async) { snprintf(err, errlen, "DeviceNAL=1 finishes the NAL units behind the queued slice writer: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1 on the device backend)"); return -1; }
     if (inp->device_input && !device_input_fn) { snprintf(err, errlen, "DeviceInput=1 pushes the source from device memory: it needs the device backend (this build has no device input: DeviceInput=0)"); return -1; }
     if (inp->device_input && inp->pipeline_depth == 1) { snprintf(err, errlen, "DeviceInput=1 pushes pictures from device memory: it needs the pipelined path (PipelineDepth=0 or > 1)"); return -1; }
     if (inp->symbol_mode && inp->profile_idc == 66) { snprintf(err, errlen, "SymbolMode=1 (CABAC) is not allowed in the Baseline profile (ProfileIDC=66)"); return -1; }

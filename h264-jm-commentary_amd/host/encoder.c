@@ -151,6 +151,11 @@ void jm_set_device_cabac_split(jm_cabac_split_fn fn) { device_cabac_split_fn = f
 static jm_coded_push_fn device_coded_push_fn;
 static jm_coded_pop_fn device_coded_pop_fn;
 void jm_set_device_coded(jm_coded_push_fn push, jm_coded_pop_fn pop) { device_coded_push_fn = push; device_coded_pop_fn = pop; }
+/* DeviceNAL 1: the whole bytes of each header go down with the push as the slice's head (device_slice
+ * _heads), the device finishes the NAL units behind the writer, and the pop brings the picture's
+ * access unit, which goes to the stream in one copy: no device_slice_assemble on this path. */
+static jm_nal_heads_fn device_nal_fn;
+void jm_set_device_nal(jm_nal_heads_fn fn) { device_nal_fn = fn; }
 
 typedef struct dcavlc {
     int n;                       /* slices per picture */
@@ -162,13 +167,14 @@ typedef struct dcavlc {
     jmh_coded_slice *cs;         /* the descriptors of either coder (the coded push takes these) */
     jmh_coded_bytes *cw;         /* where of either coder: what device_slice_assemble reads */
     jm_bits *hdr;                /* per slice: the header, then the whole RBSP */
+    jmh_nal_head *nh;            /* DeviceNAL: per slice, the header's whole bytes as the NAL unit's head */
     uint8_t *buf;                /* the device bytes (NULL in a pending picture's own dcavlc_t: they share one) */
     size_t cap;
 } dcavlc_t;
 
 static void dcavlc_free(dcavlc_t *dc) {
     if (dc->hdr) for (int i = 0; i < dc->n; i++) jm_bits_free(&dc->hdr[i]);
-    free(dc->d); free(dc->where); free(dc->cd); free(dc->cwhere); free(dc->cs); free(dc->cw); free(dc->hdr); free(dc->buf);
+    free(dc->d); free(dc->where); free(dc->cd); free(dc->cwhere); free(dc->cs); free(dc->cw); free(dc->hdr); free(dc->nh); free(dc->buf);
     memset(dc, 0, sizeof(*dc));
 }
 static int dcavlc_init(dcavlc_t *dc, const jm_seq *s, int cabac, int with_buf) {
@@ -183,9 +189,10 @@ static int dcavlc_init(dcavlc_t *dc, const jm_seq *s, int cabac, int with_buf) {
     dc->hdr = (jm_bits *)calloc(dc->n, sizeof(*dc->hdr));
     dc->cs = (jmh_coded_slice *)calloc(dc->n, sizeof(*dc->cs));
     dc->cw = (jmh_coded_bytes *)calloc(dc->n, sizeof(*dc->cw));
+    dc->nh = (jmh_nal_head *)calloc(dc->n, sizeof(*dc->nh));
     dc->cap = with_buf ? (size_t)nmb * 64 + 1024 : 0;
     dc->buf = with_buf ? (uint8_t *)malloc(dc->cap) : NULL;
-    if (!dc->d || !dc->where || !dc->cd || !dc->cwhere || !dc->cs || !dc->cw || !dc->hdr || (with_buf && !dc->buf)) { dcavlc_free(dc); return JMH_E_OOM; }
+    if (!dc->d || !dc->where || !dc->cd || !dc->cwhere || !dc->cs || !dc->cw || !dc->hdr || !dc->nh || (with_buf && !dc->buf)) { dcavlc_free(dc); return JMH_E_OOM; }
     return JMH_OK;
 }
 static int device_call(dcavlc_t *dc, jm_backend *be) {
@@ -218,6 +225,18 @@ static void device_slice_headers(dcavlc_t *dc, const jm_seq *s, const jm_slice *
         dc->d[i].lead_nbits = h->nacc;
         dc->d[i].lead_bits = (uint32_t)h->acc;
     }
+}
+/* DeviceNAL: the headers of device_slice_headers as heads (for CAVLC the partial last byte travels as
+   lead bits and comes back as the first device byte); JMH_E_INVALID_ARG: a header too long for a head */
+static int device_slice_heads(dcavlc_t *dc, const jm_slice *sl0) {
+    for (int i = 0; i < dc->n; i++) {
+        const jm_bits *h = &dc->hdr[i];
+        if (h->len > JMH_NAL_HEAD_MAX) return JMH_E_INVALID_ARG;
+        dc->nh[i].nal_ref_idc = sl0->idr ? 3 : 2; dc->nh[i].nal_unit_type = sl0->idr ? 5 : 1;
+        dc->nh[i].nbytes = (int32_t)h->len;
+        memcpy(dc->nh[i].bytes, h->buf, (size_t)h->len);
+    }
+    return JMH_OK;
 }
 /* the assemble half: header bytes + the device bytes that cw[] places in buf, per slice through
    jm_write_nal; the cabac_zero_words rule on the summed bins */
@@ -379,6 +398,10 @@ static void job_release(wpool_t *P, int k) {
 
 int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *log) {
     memset(st, 0, sizeof(*st));
+    if (inp->device_nal && !device_nal_fn) {
+        fprintf(stderr, "DeviceNAL=1 needs the device backend (backend '%s' finishes its NAL units on the host: DeviceNAL=0)\n", be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     if (inp->device_cavlc && !device_cavlc_fn) {
         fprintf(stderr, "DeviceCAVLC=1 needs the device backend (backend '%s' writes its slices on the host: DeviceCAVLC=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
@@ -442,6 +465,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     const int pipelined = dev_dbk && be->push && be->pop && be->depth > 1;
     const int depth = pipelined ? be->depth : 1;
     const int async = inp->device_writer_async;
+    const int nal = async && inp->device_nal;
     if ((async || device_input_fn) && !pipelined) {
         fprintf(stderr, "%s=1 needs the pipelined path (device deblocking, more than one picture in flight)\n", async ? "DeviceWriterAsync" : "DeviceInput");
         if (fin) fclose(fin);
@@ -532,6 +556,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         else if (inp->device_cabac) fprintf(log, " (CABAC slice data written on the device: no writer threads, no per-macroblock rate check)\n");
         if (device_input_fn) fprintf(log, " (the source is uploaded as read and pushed from device memory: the device pads it to the coded size)\n");
         if (async) fprintf(log, " (the slice writer is queued behind each picture: its pop returns the slice bytes and the SSDs)\n");
+        if (nal) fprintf(log, " (NAL units finished on the device: the pop returns the picture's access unit)\n");
         fprintf(log, " Frame  Bit/pic  QP   SnrY    SnrU    SnrV    Time(ms) MET(ms) Frm/Fld  I D\n");
     }
     double t_start = now_ms();
@@ -634,7 +659,10 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         double t1 = now_ms();                                                                      \
         jm_slice sl;                                                                               \
         PEND_SLICE(p_, sl);                                                                        \
-        device_slice_assemble(&pdc[(SLOT)], &s, &sl, dc.buf, &out);                                \
+        if (nal) {                                                                                 \
+            const dcavlc_t *d_ = &pdc[(SLOT)];                                                     \
+            jm_bits_append_bytes(&out, dc.buf, (long)(d_->cw[d_->n - 1].offset + d_->cw[d_->n - 1].nbytes)); \
+        } else device_slice_assemble(&pdc[(SLOT)], &s, &sl, dc.buf, &out);                         \
         double t2 = now_ms();                                                                      \
         st->entropy_ms += t2 - t1;                                                                 \
         long pic_bits = out.len * 8;                                                               \
@@ -705,7 +733,8 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             jm_slice sl;
             PEND_SLICE(p, sl);
             device_slice_headers(d, &s, &sl);
-            r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
+            if (nal && !(r = device_slice_heads(d, &sl))) r = device_nal_fn(be->ctx, d->n, d->nh);
+            if (!r) r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
                                 : device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
         } else
         if (!r) r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, 0, NULL, 0, 0)

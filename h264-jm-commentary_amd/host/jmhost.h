@@ -88,6 +88,10 @@ typedef struct jm_input {
                                   uploaded raw and pushed from device memory (jmh_frame_push_device /
                                   jmh_frame_push_coded_device); the device pads it to the coded size.
                                   Pipelined device backend only; the stream is the same              */
+    int  device_nal;           /* (this build) DeviceNAL 1: with DeviceWriterAsync 1 the NAL units are finished
+                                  on the device behind the slice writer (jmh_coded_nal_heads): the pop
+                                  returns the picture's Annex B access unit, appended to the stream in
+                                  one copy.  The stream is the same                                   */
     int  verbose;
 } jm_input;
 
@@ -141,6 +145,7 @@ void jm_put_se(jm_bits *b, int32_t v);
 void jm_trailing_bits(jm_bits *b);
 void jm_bits_align_flush(jm_bits *b);
 void jm_bits_append(jm_bits *b, const jm_bits *src);   /* whole bytes of src (byte aligned b) */
+void jm_bits_append_bytes(jm_bits *b, const uint8_t *src, long n);   /* the same for n bytes, in one copy */
 
 typedef struct jm_seq {
     int width, height;         /* coded */
@@ -256,6 +261,10 @@ typedef int (*jm_coded_push_fn)(void *ctx, const jm_pic *cur, const jmh_frame_pa
                                 int crop_w, int crop_h);
 typedef int (*jm_coded_pop_fn)(void *ctx, uint8_t *out, size_t cap, jmh_coded_bytes *where, jmh_coded_stats *stats);
 void jm_set_device_coded(jm_coded_push_fn push, jm_coded_pop_fn pop);
+/* DeviceNAL 1: the backend's arming of the next coded push with its slices' heads (jmh_coded_nal_heads,
+   include/jmhip_nal.h); unset on a backend without it, where the key is rejected */
+typedef int (*jm_nal_heads_fn)(void *ctx, int n, const jmh_nal_head *heads);
+void jm_set_device_nal(jm_nal_heads_fn fn);
 /* DeviceInput 1: the backend's push of a picture from device memory (jmh_frame_push_device; with n
    slices jmh_frame_push_coded_device, include/jmhip_input.h).  cur holds disp_w x disp_h samples at
    the coded picture's strides, unpadded.  Registered before jm_configure: PatchInp rejects the key

@@ -54,6 +54,7 @@ static int gpu_push_coded(void *ctx, const jm_pic *cur, const jmh_frame_params *
     if (cur->bd > 8) return jmh_frame_push_coded_u16((jmh_ctx *)ctx, cur->Y, cur->U, cur->V, cur->w, cur->w / 2, fp, n, sl, cw, ch);
     return jmh_frame_push_coded((jmh_ctx *)ctx, cur->y, cur->u, cur->v, cur->w, cur->w / 2, fp, n, sl, cw, ch);
 }
+static int gpu_nal_heads(void *ctx, int n, const jmh_nal_head *heads) { return jmh_coded_nal_heads((jmh_ctx *)ctx, n, heads); }
 static int gpu_pop_coded(void *ctx, uint8_t *out, size_t cap, jmh_coded_bytes *where, jmh_coded_stats *stats) {
     return jmh_frame_pop_coded((jmh_ctx *)ctx, out, cap, where, stats);
 }
@@ -109,6 +110,7 @@ int main(int argc, char **argv) {
     jm_set_device_cabac(gpu_cabac_slices);
     jm_set_device_cabac_split(gpu_cabac_split);
     jm_set_device_coded(gpu_push_coded, gpu_pop_coded);
+    jm_set_device_nal(gpu_nal_heads);
     if (getenv("JMH_HOST_DEBLOCK")) be.read_deblocked = NULL, be.reference_deblocked = NULL;
     jm_stats st;
     r = jm_encode_sequence(&inp, &be, &st, stdout);

@@ -264,6 +264,47 @@ _SIGS_INPUT = {
 EXPORTED_INPUT = tuple(_SIGS_INPUT)
 
 
+# ---- NAL units finished on the device (include/jmhip_nal.h; additive to ABI 14) ----
+JMH_NAL_HEAD_MAX = 64
+
+
+class JmhNalHead(ctypes.Structure):
+    _fields_ = [("nal_ref_idc", ctypes.c_int32), ("nal_unit_type", ctypes.c_int32), ("nbytes", ctypes.c_int32),
+                ("bytes", ctypes.c_uint8 * JMH_NAL_HEAD_MAX)]
+
+
+class JmhNalRange(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("nbytes", ctypes.c_int64)]
+
+
+_SIGS_NAL = {
+    "jmh_nal_geometry": (_I, [_P, _P]),
+    "jmh_nal_wrap": (_I, [_P, _I, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_size_t, _P, _P]),
+    "jmh_coded_nal_heads": (_I, [_P, _I, _P]),
+}
+EXPORTED_NAL = tuple(_SIGS_NAL)
+
+
+def nal_geometry():
+    """jmh_nal_geometry: (tile_bytes, chunk_bytes) of the NAL kernels.  Needs no device."""
+    t, c = ctypes.c_int(), ctypes.c_int()
+    _check(load().jmh_nal_geometry(ctypes.byref(t), ctypes.byref(c)), "jmh_nal_geometry")
+    return t.value, c.value
+
+
+def nal_heads(heads):
+    """A JmhNalHead array from (nal_ref_idc, nal_unit_type, bytes) triples; a head holds at most
+    JMH_NAL_HEAD_MAX bytes."""
+    a = (JmhNalHead * len(heads))()
+    for i, (ref_idc, typ, data) in enumerate(heads):
+        data = bytes(data)
+        if len(data) > JMH_NAL_HEAD_MAX:
+            raise ValueError(f"head {i}: {len(data)} bytes exceed JMH_NAL_HEAD_MAX")
+        a[i].nal_ref_idc, a[i].nal_unit_type, a[i].nbytes = ref_idc, typ, len(data)
+        ctypes.memmove(a[i].bytes, data, len(data))
+    return a
+
+
 def _addr(p):
     """A device address: an int, or any object with data_ptr() (a torch tensor, for one; that
     interoperation is not tested: the tests here do not load a second HIP runtime)."""
@@ -386,7 +427,7 @@ def load(path=LIB_PATH):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()) + \
-            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()):
+            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()) + list(_SIGS_NAL.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -518,10 +559,48 @@ class Encoder:
         return self.results(), self.recon()
 
     # ---- coded pictures (jmh_frame_push_coded / jmh_frame_pop_coded) ----
-    def push_coded(self, y, u, v, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0):
+    def _arm(self, heads):
+        """jmh_coded_nal_heads: heads (a JmhNalHead array, see nal_heads, or its triples) for the next coded push."""
+        if heads is not None:
+            if not isinstance(heads, ctypes.Array):
+                heads = nal_heads(heads)
+            _check(self.lib.jmh_coded_nal_heads(self.ctx, len(heads), ctypes.cast(heads, _P)), "jmh_coded_nal_heads")
+
+    def nal_wrap(self, heads, payload, where, nbins=0, cap=None):
+        """jmh_nal_wrap, the unit seam: heads as for nal_heads, payload bytes, where = [(offset, nbytes)]
+        of each unit's payload; nbins > 0 asks for the cabac_zero_words.  Returns (the access unit's
+        bytes, [(offset, nbytes)] of each NAL unit in them).  cap: the size of the output buffer; an
+        access unit that needs more raises JmhError (JMH_E_INVALID_ARG, .where and .total filled).
+        Without cap the buffer grows to the counted size and the call is repeated."""
+        if not isinstance(heads, ctypes.Array):
+            heads = nal_heads(heads)
+        n = len(heads)
+        pay = np.frombuffer(bytes(payload), np.uint8) if len(payload) else np.zeros(1, np.uint8)
+        wi, wo, total = (JmhNalRange * n)(), (JmhNalRange * n)(), ctypes.c_int64()
+        for i, (off, nb) in enumerate(where):
+            wi[i].offset, wi[i].nbytes = off, nb
+        size = cap if cap is not None else 3 * len(payload) // 2 + n * (2 * JMH_NAL_HEAD_MAX + 5)
+        while True:
+            out = np.zeros(max(size, 1), np.uint8)
+            st = self.lib.jmh_nal_wrap(self.ctx, n, ctypes.cast(heads, _P), _ptr(pay), ctypes.cast(wi, _P), nbins, _ptr(out), size,
+                                       ctypes.cast(wo, _P), ctypes.byref(total))
+            if st == JMH_E_INVALID_ARG and cap is None and total.value > size:
+                size = total.value
+                continue
+            break
+        wl = [(w.offset, w.nbytes) for w in wo]
+        if st != JMH_OK:
+            e = JmhError(f"jmh_nal_wrap: {STATUS.get(st, st)} ({st})")
+            e.status, e.where, e.total = st, wl, total.value
+            raise e
+        return out[:total.value].tobytes(), wl
+
+    def push_coded(self, y, u, v, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0, heads=None):
         """jmh_frame_push with the picture's slices (a JmhCodedSlice array, see coded_slice_descs): its
         slice data is written on the device behind its last macroblock.  crop: (width, height) of
-        the distortion sums, default the coded size."""
+        the distortion sums, default the coded size.  heads: one per slice (see nal_heads): the
+        picture's pop_coded then returns its NAL units, start codes included."""
+        self._arm(heads)
         fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
         y, u, v = self._planes(y, u, v)
         cw, ch = crop if crop is not None else (self.w, self.h)
@@ -605,8 +684,9 @@ class Encoder:
         s = pic.struct()
         _check(self.lib.jmh_frame_push_device(self.ctx, ctypes.byref(s), ctypes.byref(fp)), "jmh_frame_push_device")
 
-    def push_coded_device(self, pic, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0):
+    def push_coded_device(self, pic, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0, heads=None):
         """jmh_frame_push_coded_device: push_coded() of a DevicePicture."""
+        self._arm(heads)
         fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
         cw, ch = crop if crop is not None else (self.w, self.h)
         self._coded_n = getattr(self, "_coded_n", [])

@@ -38,7 +38,9 @@
  * Coded pictures (a pipelined picture whose slice data is written behind its last macroblock and
  * whose pop returns the slice bytes and the distortion only): include/jmhip_coded.h, included
  * last, additive as well.  Pictures that are already on the device (planar, NV12, P010; padded to
- * the coded size by the library): include/jmhip_input.h, additive as well.
+ * the coded size by the library): include/jmhip_input.h, additive as well.  NAL units finished on
+ * the device, so that a coded picture's pop returns its Annex B access unit: include/jmhip_nal.h,
+ * additive as well.
  *
  * Conventions: plain C types only; 0 = OK, negative JMH_E_* on error; nothing throws or aborts
  * across this boundary.  One context = one HIP device + one HIP stream; a context is not
@@ -382,4 +384,5 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #include "jmhip_coded.h"
 #include "jmhip_cabac_split.h"
 #include "jmhip_input.h"
+#include "jmhip_nal.h"
 #endif /* JMHIP_H */

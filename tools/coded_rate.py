@@ -4,10 +4,12 @@ show", §5.6): a handful of source pictures resident on the device are pushed ro
 push_coded_device / pop_coded, so no picture waits for a source.  Reports ms per picture (wall
 clock over the timed pictures, ending in the last pop) and the host time spent inside the push and
 pop calls.  --source host pushes the same pictures from host memory (push_coded): the comparison
-for the push's host time; JMH_LIB_PATH selects another build of the library for it.
+for the push's host time; JMH_LIB_PATH selects another build of the library for it.  --nal arms every
+picture with one head per slice (jmh_coded_nal_heads): its pop returns the finished access unit.
 
   python tools/coded_rate.py --config 5 --split 1024     # 2160p High 10 EPZS, RDO, CABAC, 240-MB slices
   python tools/coded_rate.py --config 2                  # 1080p Baseline FFS, CAVLC
+  python tools/coded_rate.py --config 5 --split 1024 --nal   # the same, NAL units finished on the device
 One JSON line on stdout."""
 import argparse
 import importlib.util
@@ -39,6 +41,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--source", choices=("device", "host"), default="device")
     ap.add_argument("--format", choices=("planar", "semi"), default="planar", help="device source: I420 / I010, or NV12 / P010 (10 bits only)")
+    ap.add_argument("--nal", action="store_true", help="arm every picture with its slices' heads: the pop returns the access unit")
     a = ap.parse_args()
     c = CONFIGS[a.config]
     dw, dh = (int(v) for v in a.size.split("x")) if a.size else c["disp"]
@@ -47,6 +50,8 @@ def main():
     bd = kw.get("bit_depth", 8)
     if a.source == "host" and os.environ.get("JMH_LIB_PATH"):
         jm._SIGS_INPUT.clear()                   # an older build of the library has no device-picture entry points to bind
+    if not a.nal and os.environ.get("JMH_LIB_PATH"):
+        jm._SIGS_NAL.clear()                     # nor the NAL ones
     enc = jm.Encoder(W, H, **kw)
     if a.split:
         enc.cabac_split(a.split)
@@ -58,6 +63,9 @@ def main():
                for f in frames]
     nmb = enc.mbw * enc.mbh
     descs = {st: jm.coded_slice_descs(nmb, st, QP, kw.get("slice_mbs", 0)) for st in (jm.JMH_I_SLICE, jm.JMH_P_SLICE)}
+    # a slice header's worth of head per slice: 6 bytes, the last ones zero so that runs cross the junction
+    heads = {st: jm.nal_heads([(2 if st == jm.JMH_P_SLICE else 3, 1 if st == jm.JMH_P_SLICE else 5, bytes([0x88, 0x84, k & 0xFF, 0x21, 0, 0]))
+                               for k in range(len(descs[st]))]) if a.nal else None for st in descs}
     pending = n = nbytes = fallbacks = 0
     push_s = pop_s = 0.0
     t0 = None
@@ -83,9 +91,9 @@ def main():
         st = jm.JMH_I_SLICE if i == 0 else jm.JMH_P_SLICE
         t = time.perf_counter()
         if dev:
-            enc.push_coded_device(dev[i % len(dev)], st, QP, descs[st], crop=(dw, dh), deblock=(0, 0, 0))
+            enc.push_coded_device(dev[i % len(dev)], st, QP, descs[st], crop=(dw, dh), deblock=(0, 0, 0), heads=heads[st])
         else:
-            enc.push_coded(*frames[i % len(frames)], st, QP, descs[st], crop=(dw, dh), deblock=(0, 0, 0))
+            enc.push_coded(*frames[i % len(frames)], st, QP, descs[st], crop=(dw, dh), deblock=(0, 0, 0), heads=heads[st])
         push_s += time.perf_counter() - t
         pending += 1
     while pending:
@@ -102,7 +110,7 @@ def main():
     depth = enc.depth
     enc.close()
     print(json.dumps(dict(config=a.config, size=f"{dw}x{dh}", coded=f"{W}x{H}", source=a.source, format=jm_name(fmt) if dev else "host planes",
-                          coder="CABAC" if kw.get("rdo") else "CAVLC", cabac_split=a.split, depth=depth, pictures=n,
+                          coder="CABAC" if kw.get("rdo") else "CAVLC", cabac_split=a.split, nal=int(a.nal), depth=depth, pictures=n,
                           ms_per_picture=round(1e3 * dt / n, 4), push_host_ms=round(1e3 * push_s / a.steps, 4),
                           pop_host_ms=round(1e3 * pop_s / n, 4), bytes_per_picture=nbytes // n, fallbacks=fallbacks,
                           lib=os.path.basename(os.path.dirname(jm.LIB_PATH)) + "/" + os.path.basename(jm.LIB_PATH))))
