@@ -396,9 +396,15 @@ __device__ __forceinline__ void subpel_wave(const DevParams &d, MeS &s, int j, c
 // in block 3's stage 1 (xdec below: 1 / 0, -1 none), so wave 7 shares its SIMD in those two stages
 __device__ __forceinline__ constexpr int search_wave(int j) { return (0x6325410 >> (4 * j)) & 15; }
 
-template <int NS, bool FWD, class EV, class IDLE>
+// TAIL: work of every wave in the stage's sub-pel phase, after its search if it has one (a stage 3's:
+// the next 8x8 block's SAD strip); it may overwrite ps.sadp, which no one reads after ev
+struct NoTail {
+    __device__ __forceinline__ void operator()() const {}
+};
+
+template <int NS, bool FWD, class EV, class IDLE, class TAIL = NoTail>
 __device__ __forceinline__ void me_stage(const DevParams &d, MeS &s, PosState &ps, const SDesc (&sd)[NS], int b8, int best8x8, EV ev,
-                                         int islot, IDLE idle, int wave, int xdec = -1) {
+                                         int islot, IDLE idle, int wave, int xdec = -1, TAIL tail = TAIL{}) {
     const int lane = __lane_id();
     fence_state(ps);
     int pmx[NS], pmy[NS];
@@ -436,6 +442,7 @@ __device__ __forceinline__ void me_stage(const DevParams &d, MeS &s, PosState &p
 #pragma unroll
     for (int j = 0; j < NS; j++)
         if (wave == search_wave(j)) subpel_wave(d, s, j, sd[j], pmx[j], pmy[j], ps.scx, ps.scy, b8, best8x8);
+    tail();
     if constexpr (NS <= 5) {   // wave 3 has no search: intra slot 11, decision xdec
         if (xdec >= 0 && wave == 3) idle(11, xdec);
     }
@@ -528,12 +535,28 @@ __device__ __forceinline__ void sad_strip(const MeS &s, PosState &ps) {
     }
 }
 
-// one 8x8 block of P8x8: its 4x4 SADs, 4 stages (sub-modes 4..7 in parallel, then the 4x4
-// chain), then the P8x8 sub-mode decision for the block (its MVs are read through best8x8).
-// Every block leaves its 8x8 SAD (the sum of its 4x4 SADs) in the LDS 8x8 table, so block 3 also
-// runs the 16x16 / 16x8 / 8x16 searches, which are independent of P8x8: the first blocks of each
-// type in its stage 0, the second ones in its stage 1.  Intra4x4 slots 0..10 (waves 6, 7) run in
-// the sub-pel phases of the stages listed below.
+// the four 4x4 SADs of 8x8 block B8 at this thread's positions into ps.sadp, and the block's 8x8 SAD
+// (their sum) into its 16-bit half of the 8x8 table entry (each thread reads only its own entries:
+// no barrier)
+template <int B8>
+__device__ __forceinline__ void block_strip(MeS &s, PosState &ps, int tid) {
+    sad_strip<false, 8 * (B8 & 1), 8 * (B8 >> 1), 0, 0>(s, ps);
+#pragma unroll
+    for (int k = 0; k < NPK; k++) {
+        const uint32_t a = ps.sadp[k][0], b = ps.sadp[k][1];
+        reinterpret_cast<uint16_t *>(&s.hs.sad8[k * NTA + tid])[B8] = (uint16_t)((a & 0xFFFFu) + (a >> 16) + (b & 0xFFFFu) + (b >> 16));
+    }
+}
+
+// one 8x8 block of P8x8: 4 stages (sub-modes 4..7 in parallel, then the 4x4 chain) on the block's
+// 4x4 SADs, then the P8x8 sub-mode decision for the block (its MVs are read through best8x8).
+// Block 0 computes its SADs itself; every block computes the next one's in the sub-pel phase of its
+// stage 3, whose single search leaves seven waves idle and whose full-pel argmin was the last
+// reader of its own: the search's wave after its search, the others at once.  Every block's strip
+// leaves its 8x8 SAD in the LDS 8x8 table, so block 3 also runs the 16x16 / 16x8 / 8x16 searches,
+// which are independent of P8x8: the first blocks of each type in its stage 0, the second ones in
+// its stage 1.  Intra4x4 slots 0..10 (waves 6, 7) run in the sub-pel phases of the stages listed
+// below.
 template <int B8, class IDLE>
 __device__ __forceinline__ void p8x8_block(const DevParams &d, MeS &s, PosState &ps, int &best8x8, int &cost8x8, IDLE idle, int wave, int tid) {
     constexpr int X = 2 * (B8 & 1), Y = 2 * (B8 >> 1);
@@ -548,14 +571,9 @@ __device__ __forceinline__ void p8x8_block(const DevParams &d, MeS &s, PosState 
     // on waves 2 and 3, stretched that stage by 2 us and measured slower.
     constexpr int XD0 = B8 == 0 ? 1 : -1;
     const int sr = d.sr;
-    fence_state(ps);
-    sad_strip<false, 4 * X, 4 * Y, 0, 0>(s, ps);        // the four 4x4 SADs of this 8x8 block
-    // this block's 8x8 SAD into its 16-bit half of the 8x8 table entry (each thread reads only its
-    // own entries: no barrier)
-#pragma unroll
-    for (int k = 0; k < NPK; k++) {
-        const uint32_t a = ps.sadp[k][0], b = ps.sadp[k][1];
-        reinterpret_cast<uint16_t *>(&s.hs.sad8[k * NTA + tid])[B8] = (uint16_t)((a & 0xFFFFu) + (a >> 16) + (b & 0xFFFFu) + (b >> 16));
+    if constexpr (B8 == 0) {
+        fence_state(ps);
+        block_strip<0>(s, ps, tid);
     }
     if constexpr (B8 == 3) {
         // stage 0: 8x8, 8x4 upper, 4x8 left, 4x4 top-left + 16x16, 16x8 upper, 8x16 left
@@ -601,10 +619,11 @@ __device__ __forceinline__ void p8x8_block(const DevParams &d, MeS &s, PosState 
         me_stage<1, true>(d, s, ps, sd, B8, best8x8, [&](unsigned (&bk)[1], const int (&pmx)[1], const int (&pmy)[1]) { EV(0, 7, X, Y + 1); },
                           IS2, idle, wave);
     }
-    {   // stage 3: 4x4 bottom-right
+    {   // stage 3: 4x4 bottom-right; under its sub-pel search, the next block's SADs
         const SDesc sd[1] = {{7, X + 1, Y + 1, B8, 0, 0, 0, 0}};
-        me_stage<1, true>(d, s, ps, sd, B8, best8x8, [&](unsigned (&bk)[1], const int (&pmx)[1], const int (&pmy)[1]) { EV(0, 7, X + 1, Y + 1); },
-                          IS3, idle, wave);
+        auto ev = [&](unsigned (&bk)[1], const int (&pmx)[1], const int (&pmy)[1]) { EV(0, 7, X + 1, Y + 1); };
+        if constexpr (B8 < 3) me_stage<1, true>(d, s, ps, sd, B8, best8x8, ev, IS3, idle, wave, -1, [&]() { block_strip<B8 + 1>(s, ps, tid); });
+        else me_stage<1, true>(d, s, ps, sd, B8, best8x8, ev, IS3, idle, wave);
     }
     int mc8 = BIGCOST, bm = 0;
     for (int mode = 4; mode <= 7; mode++) {

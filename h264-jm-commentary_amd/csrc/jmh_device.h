@@ -231,13 +231,13 @@ __host__ __device__ __forceinline__ size_t ffs_slot_bytes(int sr) {
 static_assert(sizeof(TickArgs) <= 4096, "TickArgs is passed by value in the kernel argument segment");
 
 // ---------------------------------------------------------------------------------------------
-//  Dataflow wavefront (k_mb_flow, SearchMode 0 with 8-bit samples, RDO off): one persistent launch
-//  per segment of ticks.  The host flattens the segment's ticks into a list of macroblocks in tick
-//  order; a workgroup claims the next one with an atomic ticket, waits until the macroblocks it
-//  depends on are done (per-MB flags), and runs its whole encode_one_macroblock -- motion search,
-//  intra decisions, the final -- before publishing its own flag.  Every dependency precedes the
-//  MB in tick order, and every claimed ticket belongs to a resident workgroup, so the wait always
-//  ends.
+//  Dataflow wavefront (k_mb_flow, SearchMode 0 with 8-bit samples, RDO off): one launch per
+//  segment of ticks, one workgroup per macroblock.  The host flattens the segment's ticks into a list
+//  of macroblocks in tick order; a workgroup claims the next one with an atomic ticket when it
+//  starts, waits until the macroblocks it depends on are done (per-MB flags), and runs its whole
+//  encode_one_macroblock -- motion search, intra decisions, the final -- before publishing its own
+//  flag.  Every dependency precedes the MB in tick order, and every claimed ticket belongs to a
+//  resident workgroup, so the wait always ends.
 // ---------------------------------------------------------------------------------------------
 // per ring entry, copied to the device with each segment: the picture's parameters and the flag
 // generations that mark its macroblocks (and its reference picture's) done
