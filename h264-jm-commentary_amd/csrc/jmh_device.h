@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/jmhip.h"
+#include "jmh_rgb.h"
 
 #define SRMAX 32                         // LDS-resident FFS window: SearchRange <= 32
 #define SIDE_MAX (2 * SRMAX + 1)
@@ -278,6 +279,15 @@ struct IngestArgs {
     int w, h, W, H;
     uint32_t maxv;
     unsigned long long *clamped;         // I010: samples above maxv are added here
+};
+
+// k_ingest_rgb (jmh_rgb.hip): an RGB device picture of w x h pixels converted into the packed W x H source
+struct RgbArgs {
+    const uint8_t *src;                  // plane[0] of the caller (jmhip_rgb.h): one dword per pixel
+    int64_t stride;                      // bytes per row
+    uint8_t *dst;                        // Y, U, V of the coded size, samples of 1 or 2 bytes
+    int w, h, W, H;
+    jmr_coef k;                          // the conversion of the format's flags at the context's bit depth
 };
 
 // XCD-aware block order.  Workgroups are dispatched round-robin over the 8 XCDs (hardware block b

@@ -24,6 +24,7 @@
 #include "jmh_cabac.h"
 #include "jmh_cabac_rate.h"
 #include "jmh_ingest.h"
+#include "jmh_rgb.h"
 #include "jmh_nal.h"
 
 // Coded pictures: bytes of output per macroblock that a picture's writer is queued with, unless
@@ -1244,10 +1245,15 @@ static int alloc_coded(jmh_ctx *c, PicBuf &b) {
 // the source of a pushed picture: host planes (strides in samples) or a device picture
 struct PushSrc { const void *y, *u, *v; int sy, sc; bool wide; const jmh_device_picture *dev; };
 
+// the argument rules of jmhip_input.h (formats 0..3, no flag) and of jmhip_rgb.h (16..19 with their flags)
 static int check_device_pic(const jmh_ctx *c, const jmh_device_picture *p) {
-    if (!p || jmi_check(p->format, p->width, p->height, c->W, c->H, p->plane, p->stride)) return JMH_E_INVALID_ARG;
+    if (!p) return JMH_E_INVALID_ARG;
+    if (jmr_is_rgb(p->format) ? jmr_check(p->format, p->width, p->height, c->W, c->H, p->plane, p->stride)
+                              : jmi_check(p->format, p->width, p->height, c->W, c->H, p->plane, p->stride)) return JMH_E_INVALID_ARG;
     return JMH_OK;
 }
+// whether a context of this bit depth takes the (checked) format
+static bool device_depth_ok(const jmh_ctx *c, int format) { return jmr_is_rgb(format) ? jmr_depth_ok(format, c->bd) : jmi_depth_ok(format, c->bd); }
 
 // k_ingest of p into dst on the context's stream, behind the work queued on the caller's stream so
 // far (ev: that stream's event); slot: the clamp word of an I010 picture
@@ -1255,6 +1261,14 @@ static int ingest_queue(jmh_ctx *c, const jmh_device_picture *p, uint8_t *dst, i
     if (p->stream) {
         HCHK(hipEventRecord(ev, (hipStream_t)p->stream));
         HCHK(hipStreamWaitEvent(c->st, ev, 0));
+    }
+    if (jmr_is_rgb(p->format)) {   // k_ingest_rgb: one plane, nothing counted
+        RgbArgs g;
+        g.src = (const uint8_t *)p->plane[0]; g.stride = p->stride[0];
+        g.dst = dst; g.w = p->width; g.h = p->height; g.W = c->W; g.H = c->H;
+        jmr_coefficients(p->format, c->bd, &g.k);
+        HCHK(jmh_launch_ingest_rgb(p->format, g, c->st));
+        return JMH_OK;
     }
     IngestArgs a;
     for (int i = 0; i < 3; i++) { a.plane[i] = (const uint8_t *)p->plane[i]; a.stride[i] = p->stride[i]; }
@@ -1280,7 +1294,7 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
     if (s.dev) { if ((r = check_device_pic(c, s.dev))) return r; }
     else if (!s.y || !s.u || !s.v || s.sy < c->W || s.sc < c->Wc) return JMH_E_INVALID_ARG;
     if ((r = check_params(c, fp))) return r;
-    if ((r = s.dev ? (jmi_depth_ok(s.dev->format, c->bd) ? JMH_OK : JMH_E_UNSUPPORTED_CFG) : check_pic(c, s.wide))) return r;
+    if ((r = s.dev ? (device_depth_ok(c, s.dev->format) ? JMH_OK : JMH_E_UNSUPPORTED_CFG) : check_pic(c, s.wide))) return r;
     std::vector<uint8_t> descs;
     if (cp) {   // before anything is claimed or queued
         if (cp->cw <= 0 || cp->ch <= 0 || cp->cw > c->W || cp->ch > c->H) return JMH_E_INVALID_ARG;
@@ -1747,7 +1761,7 @@ extern "C" int jmh_ingest_picture(jmh_ctx *c, const jmh_device_picture *pic, voi
     if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
     int r = check_device_pic(c, pic);
     if (r) return r;
-    if (!jmi_depth_ok(pic->format, c->bd)) return JMH_E_UNSUPPORTED_CFG;
+    if (!device_depth_ok(c, pic->format)) return JMH_E_UNSUPPORTED_CFG;
     HCHK(hipSetDevice(c->dev));
     DevTemps t;
     uint8_t *d = nullptr;
@@ -1765,6 +1779,17 @@ extern "C" int jmh_ingest_picture(jmh_ctx *c, const jmh_device_picture *pic, voi
     HCHK(hipMemcpy(h.data(), d, c->fsize, hipMemcpyDeviceToHost));
     unpack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps);
     c->last_clamped = pic->format == JMH_PIX_I010 ? c->h_clamp[c->nring] : 0;
+    return JMH_OK;
+}
+
+// the conversion of an RGB format (include/jmhip_rgb.h): needs no context
+extern "C" int jmh_rgb_coefficients(int format, int bit_depth, int32_t out[12]) {
+    if (!out || !jmr_is_rgb(format)) return JMH_E_INVALID_ARG;
+    if (!jmr_depth_ok(format, bit_depth)) return JMH_E_UNSUPPORTED_CFG;
+    jmr_coef k;
+    jmr_coefficients(format, bit_depth, &k);
+    memcpy(out, k.c, sizeof(k.c));
+    out[9] = k.yo; out[10] = k.co; out[11] = k.maxv;
     return JMH_OK;
 }
 

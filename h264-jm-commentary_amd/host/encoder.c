@@ -425,6 +425,18 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fprintf(stderr, "DeviceInput=1 needs the device backend (backend '%s' has no device input: DeviceInput=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
     }
+    const int rgb_format = inp->device_input_format ? inp->device_input_format | (inp->device_input_matrix ? JMH_PIX_BT709 : 0) |
+                                                          (inp->device_input_full ? JMH_PIX_FULL_RANGE : 0) : 0;
+    const jm_device_push_rgb_fn device_input_rgb_fn = rgb_format ? jm_device_input_rgb() : NULL;
+    if (rgb_format && (!device_input_fn || !device_input_rgb_fn)) {
+        fprintf(stderr, "DeviceInputFormat=%d needs DeviceInput=1 on the device backend (backend '%s' has no RGB device input: DeviceInputFormat=0)\n",
+                inp->device_input_format, be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
+    if (rgb_format && !inp->device_writer_async) {
+        fprintf(stderr, "DeviceInputFormat=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n", inp->device_input_format);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     if (inp->device_writer_async && !(device_coded_push_fn && device_coded_pop_fn)) {
         fprintf(stderr, "DeviceWriterAsync=1 needs the device backend (backend '%s' has no coded push / pop: DeviceWriterAsync=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
@@ -454,6 +466,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     FILE *fin = NULL, *fout = NULL, *frec = NULL;
     uint64_t seed = 0;
     int synthetic = !strncmp(inp->infile, "synthetic:", 10);
+    if (synthetic && rgb_format) { fprintf(stderr, "DeviceInputFormat=%d reads RGB frames from InputFile: the synthetic source is YUV\n", inp->device_input_format); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic) seed = strtoull(inp->infile + 10, NULL, 10);
     else if (!(fin = fopen(inp->infile, "rb"))) { fprintf(stderr, "Input file %s does not exist\n", inp->infile); return JMH_E_INVALID_ARG; }
     if (!(fout = fopen(inp->outfile, "wb"))) { fprintf(stderr, "Cannot open output file %s\n", inp->outfile); if (fin) fclose(fin); return JMH_E_INVALID_ARG; }
@@ -482,11 +495,15 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     pend_t *pend = (pend_t *)calloc(plen, sizeof(pend_t));
     jm_pic rec;
     memset(&rec, 0, sizeof(rec));
-    int alloc_fail = !pend || jm_pic_alloc_bd(&rec, W, H, bd);
+    /* DeviceInputFormat: one frame as read, height rows of 4 * width bytes (free again when its upload returns) */
+    const size_t rgb_bytes = (size_t)4 * inp->width * inp->height;
+    uint8_t *rgb = rgb_format ? (uint8_t *)malloc(rgb_bytes) : NULL;
+    int alloc_fail = !pend || (rgb_format && !rgb) || jm_pic_alloc_bd(&rec, W, H, bd);
     for (int k = 0; k < plen && !alloc_fail; k++) alloc_fail = jm_pic_alloc_bd(&pend[k].cur, W, H, bd);
     if (alloc_fail) {
         if (pend) for (int k = 0; k < plen; k++) jm_pic_free(&pend[k].cur);
         free(pend);
+        free(rgb);
         jm_pic_free(&rec);
         if (fin) fclose(fin);
         fclose(fout);
@@ -554,6 +571,9 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             fprintf(log, " (CABAC slice data written on the device, every slice in chunks of %d bins: no writer threads, no per-macroblock rate check)\n",
                     inp->device_cabac_split);
         else if (inp->device_cabac) fprintf(log, " (CABAC slice data written on the device: no writer threads, no per-macroblock rate check)\n");
+        if (rgb_format)
+            fprintf(log, " (the source is RGB, format %d: converted on the device with the BT.%s matrix at %s range; the stream does not signal either)\n",
+                    inp->device_input_format, inp->device_input_matrix ? "709" : "601", inp->device_input_full ? "full" : "limited");
         if (device_input_fn) fprintf(log, " (the source is uploaded as read and pushed from device memory: the device pads it to the coded size)\n");
         if (async) fprintf(log, " (the slice writer is queued behind each picture: its pop returns the slice bytes and the SSDs)\n");
         if (nal) fprintf(log, " (NAL units finished on the device: the pop returns the picture's access unit)\n");
@@ -706,6 +726,9 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         pend_t *p = &pend[(head + count) % plen];
         int idx = inp->start_frame + f;
         double tr = now_ms();
+        if (rgb_format) {
+            if (fseek(fin, (long)rgb_bytes * idx, SEEK_SET) || fread(rgb, 1, rgb_bytes, fin) != rgb_bytes) { fprintf(stderr, "ReadOneFrame: cannot read RGB frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
+        } else
         if (synthetic) jm_synth_frame(&p->cur, inp->width, inp->height, seed, idx);
         else if (jm_read_yuv_frame(fin, &p->cur, inp->width, inp->height, idx)) { fprintf(stderr, "ReadOneFrame: cannot read frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
         read_ms += now_ms() - tr;
@@ -734,7 +757,8 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             PEND_SLICE(p, sl);
             device_slice_headers(d, &s, &sl);
             if (nal && !(r = device_slice_heads(d, &sl))) r = device_nal_fn(be->ctx, d->n, d->nh);
-            if (!r) r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
+            if (!r) r = rgb_format ? device_input_rgb_fn(be->ctx, rgb, rgb_format, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
+                  : device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
                                 : device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
         } else
         if (!r) r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, 0, NULL, 0, 0)
@@ -819,6 +843,7 @@ cleanup:
     free(res);
     for (int k = 0; k < plen; k++) jm_pic_free(&pend[k].cur);
     free(pend);
+    free(rgb);
     jm_pic_free(&rec);
     if (fin) fclose(fin);
     fclose(fout);

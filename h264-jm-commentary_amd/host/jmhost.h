@@ -88,6 +88,12 @@ typedef struct jm_input {
                                   uploaded raw and pushed from device memory (jmh_frame_push_device /
                                   jmh_frame_push_coded_device); the device pads it to the coded size.
                                   Pipelined device backend only; the stream is the same              */
+    int  device_input_format;  /* (this build) DeviceInputFormat 16..19: with DeviceInput 1 InputFile holds RGB frames
+                                  (height rows of 4 * width bytes: BGRA8, RGBA8, RGB10A2, BGR10A2 of
+                                  include/jmhip_rgb.h), uploaded raw and converted on the device; 0: YUV.
+                                  Needs DeviceWriterAsync 1 (the distortion comes from the device's SSDs) */
+    int  device_input_matrix;  /* (this build) DeviceInputMatrix 1: BT.709 (0: BT.601); RGB formats only        */
+    int  device_input_full;    /* (this build) DeviceInputFullRange 1: full range (0: limited); RGB formats only */
     int  device_nal;           /* (this build) DeviceNAL 1: with DeviceWriterAsync 1 the NAL units are finished
                                   on the device behind the slice writer (jmh_coded_nal_heads): the pop
                                   returns the picture's Annex B access unit, appended to the stream in
@@ -273,6 +279,12 @@ typedef int (*jm_device_push_fn)(void *ctx, const jm_pic *cur, int disp_w, int d
                                  const jmh_coded_slice *slices, int crop_w, int crop_h);
 void jm_set_device_input(jm_device_push_fn fn);
 jm_device_push_fn jm_device_input(void);
+/* DeviceInputFormat 16..19: the backend's push of an RGB picture (jmh_frame_push_coded_device with a
+   format of include/jmhip_rgb.h, flags included).  rgb holds disp_h rows of 4 * disp_w bytes */
+typedef int (*jm_device_push_rgb_fn)(void *ctx, const void *rgb, int format, int disp_w, int disp_h, const jmh_frame_params *fp, int n,
+                                     const jmh_coded_slice *slices, int crop_w, int crop_h);
+void jm_set_device_input_rgb(jm_device_push_rgb_fn fn);
+jm_device_push_rgb_fn jm_device_input_rgb(void);
 /* 10 log10(peak^2 w h / ssd) with psnr_pl's arithmetic (99.0 at ssd 0): the PSNR of a w x h plane of
    bit_depth-bit samples from its summed squared error */
 double jm_psnr_from_ssd(uint64_t ssd, int w, int h, int bit_depth);

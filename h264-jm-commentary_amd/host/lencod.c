@@ -83,6 +83,26 @@ static int gpu_push_device(void *ctx, const jm_pic *cur, int dw, int dh, const j
     pic.stream = gpu_in.stream;
     return n ? jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch) : jmh_frame_push_device((jmh_ctx *)ctx, &pic, fp);
 }
+/* DeviceInputFormat 16..19: the RGB frame as read, through the same buffer and stream; the device converts it */
+static int gpu_push_device_rgb(void *ctx, const void *rgb, int format, int dw, int dh, const jmh_frame_params *fp, int n, const jmh_coded_slice *sl,
+                               int cw, int ch) {
+    const size_t bytes = (size_t)4 * dw * dh;
+    int r;
+    if (!gpu_in.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_in.stream))) return r;
+    if (gpu_in.bytes < bytes) {
+        if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_in.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_in.buf))) return r;
+        gpu_in.bytes = bytes;
+    }
+    if ((r = jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, rgb, bytes, gpu_in.stream))) return r;
+    jmh_device_picture pic;
+    memset(&pic, 0, sizeof(pic));
+    pic.format = format;
+    pic.width = dw; pic.height = dh;
+    pic.plane[0] = gpu_in.buf;
+    pic.stride[0] = (int64_t)4 * dw;
+    pic.stream = gpu_in.stream;
+    return jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch);
+}
 static void gpu_input_release(void *ctx) {
     if (gpu_in.stream) (void)jmh_device_stream_destroy((jmh_ctx *)ctx, gpu_in.stream);
     if (gpu_in.buf) (void)jmh_device_free((jmh_ctx *)ctx, gpu_in.buf);
@@ -94,6 +114,7 @@ int main(int argc, char **argv) {
     char err[1024];
     jm_input_defaults(&inp);
     jm_set_device_input(gpu_push_device);   /* before PatchInp: it rejects DeviceInput on a backend without one */
+    jm_set_device_input_rgb(gpu_push_device_rgb);
     if (jm_configure(&inp, argc, argv, err, sizeof(err))) { fprintf(stderr, "%s\n", err); return 1; }
     jmh_config cfg;
     jm_fill_config(&inp, &cfg);

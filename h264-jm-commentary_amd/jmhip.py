@@ -285,6 +285,24 @@ _SIGS_NAL = {
 EXPORTED_NAL = tuple(_SIGS_NAL)
 
 
+# ---- RGB pictures pushed from the device (include/jmhip_rgb.h; additive to ABI 14) ----
+JMH_PIX_BGRA8, JMH_PIX_RGBA8, JMH_PIX_RGB10A2, JMH_PIX_BGR10A2 = 16, 17, 18, 19
+JMH_PIX_BT709, JMH_PIX_FULL_RANGE = 1 << 8, 1 << 9
+
+_SIGS_RGB = {
+    "jmh_rgb_coefficients": (_I, [_I, _I, _P]),
+}
+EXPORTED_RGB = list(_SIGS_RGB)
+
+
+def rgb_coefficients(format, bit_depth):
+    """jmh_rgb_coefficients: the conversion of an RGB format with its flags at a bit depth, as 12
+    ints: cyr cyg cyb, cur cug cub, cvr cvg cvb, then Yo, Co and maxv.  Needs no device."""
+    out = (ctypes.c_int32 * 12)()
+    _check(load().jmh_rgb_coefficients(format, bit_depth, out), "jmh_rgb_coefficients")
+    return [int(v) for v in out]
+
+
 def nal_geometry():
     """jmh_nal_geometry: (tile_bytes, chunk_bytes) of the NAL kernels.  Needs no device."""
     t, c = ctypes.c_int(), ctypes.c_int()
@@ -330,7 +348,7 @@ class DevicePicture:
 
 
 class HostLayout:
-    """What to_device lays out: buf (uint8, to be uploaded as one block), the planes' byte offsets
+    """What to_device and to_device_rgb lay out: buf (uint8, to be uploaded as one block), the planes' byte offsets
     in it and their strides."""
 
     def __init__(self, format, width, height, buf, offsets, strides):
@@ -371,6 +389,28 @@ def to_device(pics, format, pad_stride=0, misalign=0):
         rows = np.lib.stride_tricks.as_strided(buf[o:], (a.shape[0], rb), (st, 1))
         rows[:] = a.view(np.uint8).reshape(a.shape[0], rb)
     return HostLayout(format, w, h, buf, offsets, strides)
+
+
+def to_device_rgb(array, format, pad_stride=0, misalign=0):
+    """An RGB picture laid out as a one-plane HostLayout: array is (h, w, 4) uint8 (the bytes of every
+    pixel in memory order) or (h, w) uint32 (the packed words), format one of JMH_PIX_BGRA8 ..
+    JMH_PIX_BGR10A2 with its flags.  pad_stride: bytes added to every row (a multiple of 4, filled
+    with 0xA5); misalign: the offset in bytes of the first pixel from a 256-byte boundary of the
+    block (a multiple of 4).  Nothing lies behind the last row's 4 * w bytes."""
+    a = np.ascontiguousarray(array)
+    if a.dtype == np.uint32 and a.ndim == 2:
+        a = a.astype("<u4").view(np.uint8).reshape(a.shape[0], a.shape[1], 4)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("to_device_rgb takes an (h, w, 4) uint8 or an (h, w) uint32 array")
+    if misalign % 4 or pad_stride % 4:
+        raise ValueError("misalign and pad_stride are multiples of 4: a pixel is a dword")
+    h, w = a.shape[:2]
+    rb = 4 * w
+    stride = rb + pad_stride
+    buf = np.full(misalign + (h - 1) * stride + rb, 0xA5, np.uint8)
+    rows = np.lib.stride_tricks.as_strided(buf[misalign:], (h, rb), (stride, 1))
+    rows[:] = a.reshape(h, rb)
+    return HostLayout(format, w, h, buf, [misalign], [stride])
 
 
 def pad_to_coded(pics, cw, ch):
@@ -427,7 +467,7 @@ def load(path=LIB_PATH):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()) + \
-            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()) + list(_SIGS_NAL.items()):
+            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()) + list(_SIGS_NAL.items()) + list(_SIGS_RGB.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -669,7 +709,7 @@ class Encoder:
         _check(self.lib.jmh_device_upload(self.ctx, _addr(dst), _ptr(data), data.nbytes, stream), "jmh_device_upload")
 
     def device_picture(self, layout, stream=None, base=None):
-        """A HostLayout (to_device) uploaded: into base, or into a new allocation of exactly its
+        """A HostLayout (to_device, to_device_rgb) uploaded: into base, or into a new allocation of exactly its
         bytes (the caller frees .base).  Returns the DevicePicture."""
         if base is None:
             base = self.device_alloc(layout.buf.nbytes)

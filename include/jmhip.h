@@ -385,4 +385,5 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #include "jmhip_cabac_split.h"
 #include "jmhip_input.h"
 #include "jmhip_nal.h"
+#include "jmhip_rgb.h"
 #endif /* JMHIP_H */

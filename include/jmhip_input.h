@@ -14,7 +14,8 @@
  * sample is word >> 6); anything else answers JMH_E_UNSUPPORTED_CFG.  An I010 sample above
  * (1 << bit depth) - 1 cannot reject the picture synchronously as jmh_frame_push_u16 does: the
  * kernel stores min(sample, maxv) (what lencod's reader of 16-bit files does) and counts such
- * samples of the width x height source; jmh_device_input_clamped returns the count.
+ * samples of the width x height source; jmh_device_input_clamped returns the count.  The RGB layouts
+ * (format 16 to 19 with their flag bits, converted to 4:2:0 by the library) are jmhip_rgb.h's.
  *
  * JMH_E_INVALID_ARG, with nothing claimed or queued: a null picture or plane (plane[2] of NV12 and
  * P010 is not read), a format outside the enum, a width or height that is odd, below 2 or above
