@@ -40,12 +40,22 @@
 #include "jmh_intra8.h"
 #include "jmh_intra.h"
 #include "jmh_i4.h"
+#include "jmh_spiral.h"
 #ifdef JMH_FLOW_TU
 #include "jmh_final.h"          // k_mb_flow (jmh_flow.hip compiles this file with JMH_FLOW_TU)
 #endif
 
 #define MVB_OFF 544                           // mvbits LUT: |4*(centre+offset) - pmv| <= 256 + 259
 #define MVB_LEN 1104
+// The table's index bound.  A full-pel position is centre + offset, both within +-SR, so |4 fm| <=
+// 4 * 2 * SR; an MV is 4 fm + a sub-pel part of at most 3, so every MV and with it every predictor
+// (a median of MVs, or one of them) is within MV_ABS_MAX = 4 * 2 * SR + 3 = 259 at SR 32.  The
+// full-pel searches read [4 fm - pmv + MVB_OFF], |.| <= 256 + 259 = 515; the sub-pel candidates add
+// their own |o| <= 3 (half-pel +-2, then quarter-pel +-1), so 518 at the most, on either side.
+#define MV_ABS_MAX (4 * 2 * SRMAX + 3)
+#define MVB_ARG_MAX (4 * 2 * SRMAX + MV_ABS_MAX + 3)
+static_assert(MVB_ARG_MAX == 518 && MVB_ARG_MAX <= MVB_OFF && MVB_OFF + MVB_ARG_MAX < MVB_LEN,
+              "s.mvc holds every MV difference the full-pel and sub-pel searches can form at SRMAX");
 #define PLS (WIN_DIM_MAX * WST + 32)          // stride between the G, b, h, j planes
 #define MAXNS 7                               // searches per stage (block 0 stage 0: 3 + 4)
 
@@ -73,8 +83,11 @@ union AnalyseS {
     IntraS<uint8_t> in[4];
 };
 
+// (wave 2 takes the stamps: every wave leaves a barrier at the same instant, and wave 2 holds a
+// search only in stages of five or more, so the poll of s.pst / s.pn -- two LDS reads and a wait,
+// stamps on or off -- is on no wave that a single-search stage waits for; 'wave' is an SGPR)
 __device__ __forceinline__ void sstamp(MeS &s, int wave) {
-    if (wave == 0 && __lane_id() == 0 && s.pst && s.pn < 44) s.pst[s.pn++] = wall_clock64();
+    if (wave == 2 && __lane_id() == 0 && s.pst && s.pn < 44) s.pst[s.pn++] = wall_clock64();
 }
 
 // ======================================================================================
@@ -288,10 +301,21 @@ __device__ __forceinline__ int quad_row_satd(const MeS &s, int wbase, int obase,
     return (int)(max(t & 0xFFFFu, t >> 16) + max(u & 0xFFFFu, u >> 16));
 }
 
+// lambda * (mvbits(vx) + mvbits(vy)) of a sub-pel candidate from the LDS table (|v| <= MVB_ARG_MAX).
+// An entry is (uint16_t)__umul24(lambda, mvbits(v)) and loses nothing: lambda <= JMH_LAMBDA_MAX = 1023
+// (check_params; JM's own are <= 91) and mvbits(v) <= 2 * 9 + 3 = 21 for |v| < 1024, so the product
+// is at most 21483 < 2^16 and, both factors being below 2^24, __umul24 is the plain product.  The
+// sum of two entries is therefore lambda * mvbits(vx) + lambda * mvbits(vy) = the product with the
+// sum, which is what the searches computed before
+static_assert(JMH_LAMBDA_MAX * 21 < 65536 && MVB_LEN - MVB_OFF <= 1024 && MVB_OFF <= 1024, "lambda * mvbits fits a u16 table entry");
+__device__ __forceinline__ int subpel_rate(const MeS &s, int vx, int vy) { return (int)s.mvc[vx + MVB_OFF] + (int)s.mvc[vy + MVB_OFF]; }
+
 // SubPelBlockMotionSearch [J] of search j of the stage on ONE wave: full-pel winner from the
-// per-wave keys, then half-pel (9 candidates) and quarter-pel (8) passes.  Lane task = (candidate,
-// 4x4 sub-block), aligned groups of nsub lanes sum a candidate, the wave minimum of
-// (cost, candidate) keys is JM's strict '<' scan in candidate order.  No workgroup barrier.
+// per-wave keys (its spiral index decoded in registers, jmh_spiral.h), then half-pel (9
+// candidates) and quarter-pel (8) passes.  Lane task = (candidate, 4x4 sub-block), aligned groups
+// of nsub lanes sum a candidate and add its rate from the LDS table (subpel_rate, read before the
+// SATD), the wave minimum of (cost, candidate) keys is JM's strict '<' scan in candidate order.
+// No workgroup barrier, no global load.
 #define KOFF 4096
 __device__ __forceinline__ void subpel_wave(const DevParams &d, MeS &s, int j, const SDesc q, int pmvx, int pmvy, int scx, int scy, int b8,
                                             int best8x8) {
@@ -300,14 +324,18 @@ __device__ __forceinline__ void subpel_wave(const DevParams &d, MeS &s, int j, c
     unsigned best = s.red[0][j];
 #pragma unroll
     for (int w = 1; w < NTA / 64; w++) best = min(best, s.red[w][j]);
+    // Where the winner lives decides the allocation of the whole kernel.  k_mb_flow keeps it in vector
+    // registers, as the table load left it: in scalar ones the window-offset arithmetic moves to the
+    // scalar unit, 69 SGPRs spill where 61 did, and the kernel measured 1.2 % slower.  k_mb_analyse has
+    // no vector register to spare for that (16 B of scratch): there it is made uniform
+#ifdef JMH_FLOW_TU
     const unsigned order = best & 8191u;
+#else
+    const unsigned order = (unsigned)__builtin_amdgcn_readfirstlane((int)(best & 8191u));
+#endif
     int rx, ry;
-    if (order == 0) { rx = -scx; ry = -scy; }
-    else {   // spiral index -> position from the context's table (a scalar load, no sqrt)
-        const uint32_t e = d.ordtab[ORDTAB_SPOS + order - 1];
-        rx = (int)(int16_t)(e & 0xFFFFu);
-        ry = (int)e >> 16;
-    }
+    jms_decode_dev((int)max(order, 1u) - 1, rx, ry);   // spiral index -> position in registers (jmh_spiral.h): no load
+    if (order == 0) { rx = -scx; ry = -scy; }              // the (0,0) pre-check
     const int fmx = scx + rx, fmy = scy + ry;
     int min_mcost = had ? BIGCOST : (int)(best >> 13);
     const int lw4 = lw4_of(q.bt), lns = lw4 + lh4_of(q.bt), nsub = 1 << lns;
@@ -336,7 +364,7 @@ __device__ __forceinline__ void subpel_wave(const DevParams &d, MeS &s, int j, c
             sat += dpp<0xB1>(sat);   // the quad's rows
             sat += dpp<0x4E>(sat);
             if (val && row == 0) {
-                int cost = sat + (int)__umul24(lam, mvbits(4 * fmx + ox - pmvx) + mvbits(4 * fmy + oy - pmvy));
+                int cost = sat + subpel_rate(s, 4 * fmx + ox - pmvx, 4 * fmy + oy - pmvy);
                 if (pass == 0 && check0 && c == 0) cost -= 16 * lam;
                 kb = min(kb, ((unsigned)(cost + KOFF) << 4) | (unsigned)c);
             }
@@ -359,7 +387,7 @@ __device__ __forceinline__ void subpel_wave(const DevParams &d, MeS &s, int j, c
             sat += dpp<0xB1>(sat);   // the quad
             sat += dpp<0x4E>(sat);
             if (val && g == 0) {
-                int cost = sat + (int)__umul24(lam, mvbits(4 * fmx + ox - pmvx) + mvbits(4 * fmy + oy - pmvy));
+                int cost = sat + subpel_rate(s, 4 * fmx + ox - pmvx, 4 * fmy + oy - pmvy);
                 if (pass == 0 && check0 && c == 0) cost -= 16 * lam;
                 kb = min(kb, ((unsigned)(cost + KOFF) << 4) | (unsigned)c);
             }

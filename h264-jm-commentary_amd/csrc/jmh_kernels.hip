@@ -15,10 +15,12 @@
 //    k_tq8x8      dct_luma8x8 likewise on one wave per block; int32 headroom at 10 bits: the
 //                 largest |coefficient| x quant_coef8 is 64 * 1023 * 20972 + (1 << 26) / 3 < 2^31
 //                The per-block search seam is k_block_search (jmh_block.hip).
+//  k_spiral_positions   unit seam of the searches' spiral decode (jmh_spiral.h, jmhip_spiral.h)
 //
 // The macroblock wavefront itself is k_mb_analyse (jmh_analyse.hip) + k_mb_final (jmh_final.hip).
 #include "jmh_common.h"
 #include "jmh_launch.h"
+#include "jmh_spiral.h"
 
 // ======================================================================================
 //  quarter-pel interpolation (H.264 8.4.2.2.1), spec coordinate clamping
@@ -104,7 +106,22 @@ __global__ __launch_bounds__(256) void k_tq8x8(int n, const int16_t *resid, cons
     if (l == 0) { coeff_cost[blk] = cc; nonzero[blk] = nz != 0; }
 }
 
+// unit seam of the searches' spiral decode (jmhip_spiral.h): jms_decode_dev, the function
+// subpel_wave calls, on every index n < count; out_xy holds 2 * count words
+__global__ __launch_bounds__(256) void k_spiral_positions(int count, int32_t *__restrict__ out_xy) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= count) return;
+    int x, y;
+    jms_decode_dev(n, x, y);
+    out_xy[2 * n] = x;
+    out_xy[2 * n + 1] = y;
+}
+
 // ---- launchers (host side, same translation unit) --------------------------------------
+hipError_t jmh_launch_spiral_positions(int count, int32_t *out_xy, hipStream_t st) {
+    hipLaunchKernelGGL(k_spiral_positions, dim3((count + 255) / 256), dim3(256), 0, st, count, out_xy);
+    return hipGetLastError();
+}
 hipError_t jmh_launch_interp(const uint8_t *ref, int W, int H, uint8_t *qpel, int qstride, int qplane, hipStream_t st) {
     dim3 grid((qstride + 63) / 64, (H + 2 * QPAD + 3) / 4);
     hipLaunchKernelGGL(k_interp, grid, dim3(256), 0, st, ref, W, H, qpel, qstride, qplane);

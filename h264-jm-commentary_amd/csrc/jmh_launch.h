@@ -19,6 +19,7 @@ hipError_t jmh_launch_ingest_rgb(int format, const RgbArgs &a, hipStream_t st); 
 // the unit seams: pel = uint8_t or uint16_t samples (instantiated for both where they are defined);
 // qpb = qp + QpBdOffset, maxv = (1 << bit depth) - 1 (8 bits: qp and 255)
 hipError_t jmh_launch_interp(const uint8_t *ref, int W, int H, uint8_t *qpel, int qstride, int qplane, hipStream_t st);   // jmh_kernels.hip
+hipError_t jmh_launch_spiral_positions(int count, int32_t *out_xy, hipStream_t st);   // jmh_kernels.hip (jmhip_spiral.h)
 template <class pel>
 hipError_t jmh_launch_sad_table(const pel *org, const pel *ref, int W, int H, int sr, int n_mb, const int32_t *mb_xy, const int32_t *centres,
                                 uint16_t *out, hipStream_t st);

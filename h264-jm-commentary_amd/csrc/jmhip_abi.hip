@@ -26,6 +26,7 @@
 #include "jmh_ingest.h"
 #include "jmh_rgb.h"
 #include "jmh_nal.h"
+#include "jmh_spiral.h"
 
 // Coded pictures: bytes of output per macroblock that a picture's writer is queued with, unless
 // JMH_CODED_CAP says otherwise.  192 B per MB is about four times the densest picture recorded
@@ -644,40 +645,16 @@ int jmh_pipeline_depth(const jmh_ctx *c) { return c ? c->depth : JMH_E_INVALID_A
 
 }  // extern "C"
 
-// JM spiral order (Init_Motion_Search_Module [J]) of relative position (x, y)
-static int host_spiral_index(int x, int y) {
-    const int ax = x < 0 ? -x : x, ay = y < 0 ? -y : y, l = ax > ay ? ax : ay;
-    if (l == 0) return 0;
-    const int base = (2 * l - 1) * (2 * l - 1);
-    if (ay == l && ax < l) return base + 2 * (x + l - 1) + (y > 0);
-    return base + 2 * (2 * l - 1) + 2 * (y + l) + (x > 0);
-}
-
-// order keys of the FFS analysis threads (k_mb_analyse): thread t owns window column t % side,
-// rows (t / side) * NPK .. + NPK - 1; key = spiral index + 1 (0 is the (0,0) pre-check, set per
-// MB in the kernel), 0xFFFF outside the window.  [NPK2][NTA] packed pairs (low = even slot).  Then
-// the inverse, ORDTAB_SPOS: spiral index -> position
-// (x & 0xFFFF | y << 16), read with one scalar load where a search's winner is decoded.
+// order keys of the FFS analysis threads and the spiral tables behind them: jms_ordtab_fill of
+// jmh_spiral.h, which states JM's spiral order (Init_Motion_Search_Module [J]) for host and device.
+// k_mb_analyse and k_mb_flow read only the keys: they decode a search's winner in registers
+// (jms_decode_dev), so no load sits between a stage's argmin and its sub-pel search; the tables at
+// ORDTAB_SPOS are read by the EPZS and RDO FFS paths (jmh_epzs.h).
 static void ordtab_fill(std::vector<uint32_t> &tab, int sr) {
-    const int side = 2 * sr + 1, nstrips = (side + NPK - 1) / NPK;
     static_assert(SIDE_MAX * ((SIDE_MAX + NPK - 1) / NPK) <= NTA, "the search threads cover every FFS position");
-    // after the keys: spiral index -> position, then raster position -> spiral index (the RDO FFS
-    // table's tie order, jmh_epzs.h ffs_table_min)
-    tab.assign((size_t)ORDTAB_SPOS + (size_t)2 * side * side, 0);
-    for (int y = -sr; y <= sr; y++)
-        for (int x = -sr; x <= sr; x++) {
-            tab[(size_t)ORDTAB_SPOS + host_spiral_index(x, y)] = ((uint32_t)x & 0xFFFFu) | (uint32_t)y << 16;
-            tab[(size_t)ORDTAB_SPOS + (size_t)side * side + (size_t)(y + sr) * side + x + sr] = (uint32_t)host_spiral_index(x, y);
-        }
-    for (int t = 0; t < NTA; t++) {
-        const bool sact = t < side * nstrips;
-        const int dx = sact ? t % side : 0, dy0 = sact ? (t / side) * NPK : 0;
-        for (int k = 0; k < NPK; k++) {
-            const int dy = dy0 + k;
-            const uint32_t o = (!sact || dy >= side) ? 0xFFFFu : (uint32_t)(host_spiral_index(dx - sr, dy - sr) + 1);
-            tab[(size_t)(k >> 1) * NTA + t] |= o << (16 * (k & 1));
-        }
-    }
+    static_assert(ORDTAB_SPOS == ((NPK + 1) / 2) * NTA, "jms_ordtab_fill puts the spiral tables behind the keys");
+    tab.assign(jms_ordtab_len(sr, NPK, NTA), 0);
+    jms_ordtab_fill(tab.data(), sr, NPK, NTA);
 }
 
 // planar 4:2:0 packing of ps-byte samples (strides in samples).  16-bit samples are range-checked
@@ -1790,6 +1767,21 @@ extern "C" int jmh_rgb_coefficients(int format, int bit_depth, int32_t out[12]) 
     jmr_coefficients(format, bit_depth, &k);
     memcpy(out, k.c, sizeof(k.c));
     out[9] = k.yo; out[10] = k.co; out[11] = k.maxv;
+    return JMH_OK;
+}
+
+// the unit seam of the searches' spiral decode (include/jmhip_spiral.h): the device function on
+// every index of a search range
+extern "C" int jmh_spiral_positions(jmh_ctx *c, int search_range, int32_t *out_xy) {
+    if (!c || !out_xy || search_range < 1 || search_range > SRMAX) return JMH_E_INVALID_ARG;
+    const int side = 2 * search_range + 1, count = side * side;
+    HCHK(hipSetDevice(c->dev));
+    DevTemps tmp;
+    int32_t *d_out = nullptr;
+    if (tmp.alloc(&d_out, (size_t)count * 2 * sizeof(int32_t)) != hipSuccess) return JMH_E_OOM;
+    HCHK(jmh_launch_spiral_positions(count, d_out, c->st));
+    HCHK(hipMemcpyAsync(out_xy, d_out, (size_t)count * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->st));
+    HCHK(hipStreamSynchronize(c->st));
     return JMH_OK;
 }
 

@@ -294,6 +294,13 @@ _SIGS_RGB = {
 }
 EXPORTED_RGB = list(_SIGS_RGB)
 
+# ---- the unit seam of the searches' spiral decode (include/jmhip_spiral.h; additive to ABI 14);
+#      bound where it is called (Encoder.spiral_positions), so that a library built before it loads
+_SIGS_SPIRAL = {
+    "jmh_spiral_positions": (_I, [_P, _I, _P]),
+}
+EXPORTED_SPIRAL = tuple(_SIGS_SPIRAL)
+
 
 def rgb_coefficients(format, bit_depth):
     """jmh_rgb_coefficients: the conversion of an RGB format with its flags at a bit depth, as 12
@@ -892,6 +899,16 @@ class Encoder:
                     scratch_bytes=info.scratch_bytes, setting=self.lib.jmh_cabac_get_split(self.ctx))
 
     # ---- unit seams ----
+    def spiral_positions(self, search_range):
+        """jmh_spiral_positions (include/jmhip_spiral.h): the kernels' spiral decode on the device, as
+        an int32 array [(2 sr + 1)^2][2] of (x, y) by spiral index."""
+        fn = self.lib.jmh_spiral_positions
+        fn.restype, fn.argtypes = _SIGS_SPIRAL["jmh_spiral_positions"]
+        side = 2 * search_range + 1
+        out = np.empty((side * side, 2), np.int32)
+        _check(fn(self.ctx, search_range, _ptr(out)), "jmh_spiral_positions")
+        return out
+
     def sad_table(self, mb_xy, centres):
         mb_xy = np.ascontiguousarray(mb_xy, np.int32)
         centres = np.ascontiguousarray(centres, np.int32)
