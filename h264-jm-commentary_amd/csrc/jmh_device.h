@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/jmhip.h"
 #include "jmh_rgb.h"
+#include "jmh_tensor.h"
 
 #define SRMAX 32                         // LDS-resident FFS window: SearchRange <= 32
 #define SIDE_MAX (2 * SRMAX + 1)
@@ -289,6 +290,32 @@ struct RgbArgs {
     int w, h, W, H;
     jmr_coef k;                          // the conversion of the format's flags at the context's bit depth
 };
+
+// k_ingest_tensor (jmh_tensor.hip): a device tensor of w x h pixels quantised and converted into the packed W x H source
+struct TensorArgs {
+    const uint8_t *chan[3];              // R, G, B of the caller (jmhip_tensor.h) at pixel (0, 0)
+    int64_t sx, sy;                      // bytes between pixels / rows
+    uint8_t *dst;                        // Y, U, V of the coded size, samples of 1 or 2 bytes
+    int w, h, W, H;
+    jmr_coef k;                          // the conversion of the flags at the context's bit depth (maxv: M of the quantiser)
+};
+
+// The stores of the converting ingest kernels (k_ingest_rgb, k_ingest_tensor): 8 luma samples of a row or 4 + 4
+// chroma samples, packed little-endian; TEN: 16-bit samples
+template <bool TEN>
+__device__ __forceinline__ uint32_t ingest_pack(const int32_t *v) {
+    return TEN ? (uint32_t)v[0] | (uint32_t)v[1] << 16 : (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 | (uint32_t)v[3] << 24;
+}
+template <bool TEN>
+__device__ __forceinline__ void ingest_store_luma(uint8_t *o, const int32_t *y) {
+    if (TEN) *reinterpret_cast<uint4 *>(o) = make_uint4(ingest_pack<true>(y), ingest_pack<true>(y + 2), ingest_pack<true>(y + 4), ingest_pack<true>(y + 6));
+    else *reinterpret_cast<uint2 *>(o) = make_uint2(ingest_pack<false>(y), ingest_pack<false>(y + 4));
+}
+template <bool TEN>
+__device__ __forceinline__ void ingest_store_chroma(uint8_t *o, const int32_t *c) {
+    if (TEN) *reinterpret_cast<uint2 *>(o) = make_uint2(ingest_pack<true>(c), ingest_pack<true>(c + 2));
+    else *reinterpret_cast<uint32_t *>(o) = ingest_pack<false>(c);
+}
 
 // XCD-aware block order.  Workgroups are dispatched round-robin over the 8 XCDs (hardware block b
 // runs on XCD b % 8), each with its own L2.  A launch of n logical blocks uses 8 * ceil(n / 8)

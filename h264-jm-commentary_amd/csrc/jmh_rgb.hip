@@ -21,22 +21,6 @@
 
 #define RGB_WAVES 4
 
-// 8 luma samples of a row or 4 + 4 chroma samples, packed little-endian: TEN: 16-bit samples
-template <bool TEN>
-__device__ __forceinline__ uint32_t rgb_pack(const int32_t *v) {
-    return TEN ? (uint32_t)v[0] | (uint32_t)v[1] << 16 : (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 | (uint32_t)v[3] << 24;
-}
-template <bool TEN>
-__device__ __forceinline__ void rgb_store_luma(uint8_t *o, const int32_t *y) {
-    if (TEN) *reinterpret_cast<uint4 *>(o) = make_uint4(rgb_pack<true>(y), rgb_pack<true>(y + 2), rgb_pack<true>(y + 4), rgb_pack<true>(y + 6));
-    else *reinterpret_cast<uint2 *>(o) = make_uint2(rgb_pack<false>(y), rgb_pack<false>(y + 4));
-}
-template <bool TEN>
-__device__ __forceinline__ void rgb_store_chroma(uint8_t *o, const int32_t *c) {
-    if (TEN) *reinterpret_cast<uint2 *>(o) = make_uint2(rgb_pack<true>(c), rgb_pack<true>(c + 2));
-    else *reinterpret_cast<uint32_t *>(o) = rgb_pack<false>(c);
-}
-
 // the 2x2 block of dwords p00 p01 / p10 p11: its four luma samples and its U and V
 template <int FMT>
 __device__ __forceinline__ void rgb_block(const jmr_coef &k, uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p11, int32_t *y0, int32_t *y1,
@@ -106,10 +90,10 @@ __global__ __launch_bounds__(64 * RGB_WAVES) void k_ingest_rgb(RgbArgs a) {
 #pragma unroll
             for (int i = 0; i < 8; i++) y0[i] = y1[i];
         }
-        rgb_store_luma<TEN>(oy0 + (size_t)x0 * ES, y0);
-        rgb_store_luma<TEN>(oy1 + (size_t)x0 * ES, y1);
-        rgb_store_chroma<TEN>(ou + (size_t)(x0 / 2) * ES, u);
-        rgb_store_chroma<TEN>(ov + (size_t)(x0 / 2) * ES, v);
+        ingest_store_luma<TEN>(oy0 + (size_t)x0 * ES, y0);
+        ingest_store_luma<TEN>(oy1 + (size_t)x0 * ES, y1);
+        ingest_store_chroma<TEN>(ou + (size_t)(x0 / 2) * ES, u);
+        ingest_store_chroma<TEN>(ov + (size_t)(x0 / 2) * ES, v);
     }
 }
 

@@ -25,6 +25,7 @@
 #include "jmh_cabac_rate.h"
 #include "jmh_ingest.h"
 #include "jmh_rgb.h"
+#include "jmh_tensor.h"
 #include "jmh_nal.h"
 #include "jmh_spiral.h"
 
@@ -146,7 +147,7 @@ struct PicBuf {
     int nal_armed;                       // the occupant was armed (jmh_coded_nal_heads): its pop returns the access unit
     NalBuf nal;                          //   the entry's NAL buffers, on its first armed picture
     // device pictures (jmhip_input.h)
-    int dev_fmt;                         // the occupant was pushed from device memory: its format + 1, else 0
+    int dev_fmt;                         // the occupant was pushed as a device picture: its format + 1, else 0 (a host picture, a tensor)
     hipEvent_t ev_in;                    //   the caller's stream at the push (created on first use)
 };
 
@@ -1219,8 +1220,8 @@ static int alloc_coded(jmh_ctx *c, PicBuf &b) {
     return JMH_OK;
 }
 
-// the source of a pushed picture: host planes (strides in samples) or a device picture
-struct PushSrc { const void *y, *u, *v; int sy, sc; bool wide; const jmh_device_picture *dev; };
+// the source of a pushed picture: host planes (strides in samples), a device picture or a device tensor
+struct PushSrc { const void *y, *u, *v; int sy, sc; bool wide; const jmh_device_picture *dev; const jmh_device_tensor *ten; };
 
 // the argument rules of jmhip_input.h (formats 0..3, no flag) and of jmhip_rgb.h (16..19 with their flags)
 static int check_device_pic(const jmh_ctx *c, const jmh_device_picture *p) {
@@ -1231,6 +1232,27 @@ static int check_device_pic(const jmh_ctx *c, const jmh_device_picture *p) {
 }
 // whether a context of this bit depth takes the (checked) format
 static bool device_depth_ok(const jmh_ctx *c, int format) { return jmr_is_rgb(format) ? jmr_depth_ok(format, c->bd) : jmi_depth_ok(format, c->bd); }
+
+// the argument rules of jmhip_tensor.h
+static int check_device_tensor(const jmh_ctx *c, const jmh_device_tensor *t) {
+    if (!t || jmt_check(t->dtype, t->flags, t->width, t->height, c->W, c->H, t->chan, t->stride_x, t->stride_y)) return JMH_E_INVALID_ARG;
+    return JMH_OK;
+}
+
+// k_ingest_tensor of t into dst, queued as ingest_queue below queues a picture's kernel
+static int ingest_queue_tensor(jmh_ctx *c, const jmh_device_tensor *t, uint8_t *dst, hipEvent_t ev) {
+    if (t->stream) {
+        HCHK(hipEventRecord(ev, (hipStream_t)t->stream));
+        HCHK(hipStreamWaitEvent(c->st, ev, 0));
+    }
+    TensorArgs g;
+    for (int i = 0; i < 3; i++) g.chan[i] = (const uint8_t *)t->chan[i];
+    g.sx = t->stride_x; g.sy = t->stride_y;
+    g.dst = dst; g.w = t->width; g.h = t->height; g.W = c->W; g.H = c->H;
+    jmr_coefficients(t->flags, c->bd, &g.k);
+    HCHK(jmh_launch_ingest_tensor(t->dtype, g, c->st));
+    return JMH_OK;
+}
 
 // k_ingest of p into dst on the context's stream, behind the work queued on the caller's stream so
 // far (ev: that stream's event); slot: the clamp word of an I010 picture
@@ -1268,10 +1290,14 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
     const bool armed = c->nal_armed && cp;   // jmh_coded_nal_heads holds for one push, whatever becomes of it
     c->nal_armed = false;
     int r;
+    void *const in_stream = s.dev ? s.dev->stream : s.ten ? s.ten->stream : nullptr;   // the caller's, of a device source
+    const bool device_src = s.dev || s.ten;
     if (s.dev) { if ((r = check_device_pic(c, s.dev))) return r; }
+    else if (s.ten) { if ((r = check_device_tensor(c, s.ten))) return r; }
     else if (!s.y || !s.u || !s.v || s.sy < c->W || s.sc < c->Wc) return JMH_E_INVALID_ARG;
     if ((r = check_params(c, fp))) return r;
-    if ((r = s.dev ? (device_depth_ok(c, s.dev->format) ? JMH_OK : JMH_E_UNSUPPORTED_CFG) : check_pic(c, s.wide))) return r;
+    if ((r = s.dev ? (device_depth_ok(c, s.dev->format) ? JMH_OK : JMH_E_UNSUPPORTED_CFG)
+           : s.ten ? (jmt_depth_ok(s.ten->dtype, c->bd) ? JMH_OK : JMH_E_UNSUPPORTED_CFG) : check_pic(c, s.wide))) return r;
     std::vector<uint8_t> descs;
     if (cp) {   // before anything is claimed or queued
         if (cp->cw <= 0 || cp->ch <= 0 || cp->cw > c->W || cp->ch > c->H) return JMH_E_INVALID_ARG;
@@ -1284,20 +1310,20 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
     int e;
     if ((r = claim_entry(c, &e))) return r;
     PicBuf &b = c->ring[e];
-    if (cp) {   // no readback: the source staging only (a device picture: none)
-        if (!s.dev && !b.h_src && hipHostMalloc((void **)&b.h_src, c->fsize, hipHostMallocDefault) != hipSuccess) { b.h_src = nullptr; return JMH_E_OOM; }
+    if (cp) {   // no readback: the source staging only (a device source: none)
+        if (!device_src && !b.h_src && hipHostMalloc((void **)&b.h_src, c->fsize, hipHostMallocDefault) != hipSuccess) { b.h_src = nullptr; return JMH_E_OOM; }
         if ((r = alloc_coded(c, b))) return r;
         if (armed && (r = nal_reserve(c, b.nal, cp->n, b.cd_cap, nal_region(b.cd_cap, cp->n)))) return r;
-    } else if ((r = alloc_host(c, b, !s.dev))) return r;
-    if (s.dev) {
-        // the device picture packed and padded where a host picture is uploaded: between ev_t0 and
+    } else if ((r = alloc_host(c, b, !device_src))) return r;
+    if (device_src) {
+        // the device picture (or tensor) packed and padded where a host picture is uploaded: between ev_t0 and
         // ev_src on the context's stream.  The caller's stream then waits for ev_src, so what it
         // is given after this call may overwrite the planes
-        if (s.dev->stream && !b.ev_in && hipEventCreateWithFlags(&b.ev_in, hipEventDisableTiming) != hipSuccess) { b.ev_in = nullptr; return JMH_E_HIP; }
+        if (in_stream && !b.ev_in && hipEventCreateWithFlags(&b.ev_in, hipEventDisableTiming) != hipSuccess) { b.ev_in = nullptr; return JMH_E_HIP; }
         HCHK(hipEventRecord(b.ev_t0, c->st));
-        if ((r = ingest_queue(c, s.dev, b.src, e, b.ev_in))) return r;
+        if ((r = s.dev ? ingest_queue(c, s.dev, b.src, e, b.ev_in) : ingest_queue_tensor(c, s.ten, b.src, b.ev_in))) return r;
         HCHK(hipEventRecord(b.ev_src, c->st));
-        if (s.dev->stream) HCHK(hipStreamWaitEvent((hipStream_t)s.dev->stream, b.ev_src, 0));
+        if (in_stream) HCHK(hipStreamWaitEvent((hipStream_t)in_stream, b.ev_src, 0));
         c->last_dev_entry = e;
     } else {
         HCHK(hipEventSynchronize(b.ev_src));   // the previous H2D out of this staging buffer
@@ -1324,33 +1350,44 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
 }
 extern "C" {
 int jmh_frame_push(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp) {
-    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, nullptr}, fp);
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, nullptr, nullptr}, fp);
 }
 int jmh_frame_push_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp) {
-    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, nullptr}, fp);
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, nullptr, nullptr}, fp);
 }
 
 int jmh_frame_push_coded(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp, int n,
                          const jmh_coded_slice *slices, int crop_w, int crop_h) {
     const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, nullptr}, fp, &cp);
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, nullptr, nullptr}, fp, &cp);
 }
 int jmh_frame_push_coded_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp,
                              int n, const jmh_coded_slice *slices, int crop_w, int crop_h) {
     const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, nullptr}, fp, &cp);
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, nullptr, nullptr}, fp, &cp);
 }
 
 // ---- pictures that are already on the device (include/jmhip_input.h) ----
 int jmh_frame_push_device(jmh_ctx *c, const jmh_device_picture *pic, const jmh_frame_params *fp) {
     if (!pic) return JMH_E_INVALID_ARG;
-    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, pic}, fp);
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, pic, nullptr}, fp);
 }
 int jmh_frame_push_coded_device(jmh_ctx *c, const jmh_device_picture *pic, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
                                 int crop_w, int crop_h) {
     if (!pic) return JMH_E_INVALID_ARG;
     const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, pic}, fp, &cp);
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, pic, nullptr}, fp, &cp);
+}
+// ---- tensors that are already on the device (include/jmhip_tensor.h) ----
+int jmh_frame_push_tensor(jmh_ctx *c, const jmh_device_tensor *t, const jmh_frame_params *fp) {
+    if (!t) return JMH_E_INVALID_ARG;
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, nullptr, t}, fp);
+}
+int jmh_frame_push_coded_tensor(jmh_ctx *c, const jmh_device_tensor *t, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
+                                int crop_w, int crop_h) {
+    if (!t) return JMH_E_INVALID_ARG;
+    const CodedPush cp = {n, slices, crop_w, crop_h};
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, nullptr, t}, fp, &cp);
 }
 int jmh_device_input_wait(jmh_ctx *c) {
     if (!c) return JMH_E_INVALID_ARG;
@@ -1756,6 +1793,42 @@ extern "C" int jmh_ingest_picture(jmh_ctx *c, const jmh_device_picture *pic, voi
     HCHK(hipMemcpy(h.data(), d, c->fsize, hipMemcpyDeviceToHost));
     unpack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps);
     c->last_clamped = pic->format == JMH_PIX_I010 ? c->h_clamp[c->nring] : 0;
+    return JMH_OK;
+}
+
+// the unit seam of k_ingest_tensor: the kernel into a scratch picture, the packed planes to the host
+extern "C" int jmh_ingest_tensor(jmh_ctx *c, const jmh_device_tensor *t, void *y, void *u, void *v, int sy, int sc) {
+    if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
+    int r = check_device_tensor(c, t);
+    if (r) return r;
+    if (!jmt_depth_ok(t->dtype, c->bd)) return JMH_E_UNSUPPORTED_CFG;
+    HCHK(hipSetDevice(c->dev));
+    DevTemps tmp;
+    uint8_t *d = nullptr;
+    if (tmp.alloc(&d, c->fsize) != hipSuccess) return JMH_E_OOM;
+    hipEvent_t ev = nullptr;
+    if (t->stream) HCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    r = ingest_queue_tensor(c, t, d, ev);
+    if (!r && t->stream && (hipEventRecord(ev, c->st) != hipSuccess || hipStreamWaitEvent((hipStream_t)t->stream, ev, 0) != hipSuccess))
+        r = JMH_E_HIP;
+    const hipError_t se = hipStreamSynchronize(c->st);
+    if (ev) (void)hipEventDestroy(ev);
+    if (r) return r;
+    HCHK(se);
+    std::vector<uint8_t> h(c->fsize);
+    HCHK(hipMemcpy(h.data(), d, c->fsize, hipMemcpyDeviceToHost));
+    unpack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps);
+    c->last_clamped = 0;
+    return JMH_OK;
+}
+
+// the quantiser of a tensor's elements (include/jmhip_tensor.h) on the host: needs no context
+extern "C" int jmh_tensor_quantise(int dtype, int bit_depth, const void *elems, size_t n, int32_t *q) {
+    if (dtype < 0 || dtype >= JMT_NDTYPES || (n && (!elems || !q))) return JMH_E_INVALID_ARG;
+    if (!jmt_depth_ok(dtype, bit_depth)) return JMH_E_UNSUPPORTED_CFG;
+    const int32_t M = (1 << bit_depth) - 1;
+    const uint8_t *p = (const uint8_t *)elems;
+    for (size_t i = 0; i < n; i++) q[i] = jmt_quant(dtype, jmt_load(dtype, p + i * jmt_es(dtype)), M);
     return JMH_OK;
 }
 

@@ -74,6 +74,7 @@ static const map_entry Map[] = {
     {"DeviceInputFormat", 0, OFF(device_input_format), 0, 19},
     {"DeviceInputMatrix", 0, OFF(device_input_matrix), 0, 1},
     {"DeviceInputFullRange", 0, OFF(device_input_full), 0, 1},
+    {"DeviceInputTensor", 0, OFF(device_input_tensor), 0, 4},
     {"DeviceNAL", 0, OFF(device_nal), 0, 1},
     {"JMVersion", 0, OFF(jm_version), 8, 99},
     {"QOffsetIntra", 0, OFF(qoff_intra), -1, JMH_QOFFSET_MAX},
@@ -193,6 +194,9 @@ jm_device_push_fn jm_device_input(void) { return device_input_fn; }
 static jm_device_push_rgb_fn device_input_rgb_fn;
 void jm_set_device_input_rgb(jm_device_push_rgb_fn fn) { device_input_rgb_fn = fn; }
 jm_device_push_rgb_fn jm_device_input_rgb(void) { return device_input_rgb_fn; }
+static jm_device_push_tensor_fn device_input_tensor_fn;
+void jm_set_device_input_tensor(jm_device_push_tensor_fn fn) { device_input_tensor_fn = fn; }
+jm_device_push_tensor_fn jm_device_input_tensor(void) { return device_input_tensor_fn; }
 
 int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->rdopt > 1) { snprintf(err, errlen, "RDOptimization=%d not supported (0 or 1)", inp->rdopt); return -1; }
@@ -210,11 +214,19 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->device_input && inp->pipeline_depth == 1) { snprintf(err, errlen, "DeviceInput=1 pushes pictures from device memory: it needs the pipelined path (PipelineDepth=0 or > 1)"); return -1; }
     if (inp->device_input_format && !inp->device_input) { snprintf(err, errlen, "DeviceInputFormat=%d names the layout of a picture pushed from device memory: it needs DeviceInput=1", inp->device_input_format); return -1; }
     if (inp->device_input_format && inp->device_input_format < 16) { snprintf(err, errlen, "DeviceInputFormat=%d not supported (0: YUV, 16 BGRA8, 17 RGBA8, 18 RGB10A2, 19 BGR10A2)", inp->device_input_format); return -1; }
-    if ((inp->device_input_matrix || inp->device_input_full) && !inp->device_input_format) { snprintf(err, errlen, "DeviceInputMatrix / DeviceInputFullRange describe an RGB source: they need DeviceInput=1 and DeviceInputFormat=16..19"); return -1; }
+    if ((inp->device_input_matrix || inp->device_input_full) && !inp->device_input_format && !inp->device_input_tensor) { snprintf(err, errlen, "DeviceInputMatrix / DeviceInputFullRange describe an RGB source: they need DeviceInput=1 and DeviceInputFormat=16..19"); return -1; }
     if (inp->device_input_format && !device_input_rgb_fn) { snprintf(err, errlen, "DeviceInputFormat=%d converts the source on the device: it needs the device backend (this build has no RGB device input: DeviceInputFormat=0)", inp->device_input_format); return -1; }
     if (inp->device_input_format && inp->bit_depth_luma != (inp->device_input_format >= 18 ? 10 : 8)) { snprintf(err, errlen, "DeviceInputFormat=%d holds %d-bit components: it needs SourceBitDepthLuma=%d (got %d)", inp->device_input_format, inp->device_input_format >= 18 ? 10 : 8, inp->device_input_format >= 18 ? 10 : 8, inp->bit_depth_luma); return -1; }
     if (inp->device_input_format && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputFormat=%d reads RGB frames from InputFile: the synthetic source is YUV (InputFile=%s)", inp->device_input_format, inp->infile); return -1; }
     if (inp->device_input_format && !inp->device_writer_async) { snprintf(err, errlen, "DeviceInputFormat=%d leaves no YUV source on the host, so the distortion comes from the device's SSDs: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1)", inp->device_input_format); return -1; }
+    if (inp->device_input_tensor && !inp->device_input) { snprintf(err, errlen, "DeviceInputTensor=%d names the layout of a tensor pushed from device memory: it needs DeviceInput=1", inp->device_input_tensor); return -1; }
+    if (inp->device_input_tensor && inp->device_input_format) { snprintf(err, errlen, "DeviceInputTensor=%d and DeviceInputFormat=%d both name the layout of InputFile: set one of them", inp->device_input_tensor, inp->device_input_format); return -1; }
+    if (inp->device_input_tensor && !device_input_tensor_fn) { snprintf(err, errlen, "DeviceInputTensor=%d quantises and converts the source on the device: it needs the device backend (this build has no tensor device input: DeviceInputTensor=0)", inp->device_input_tensor); return -1; }
+    if (inp->device_input_tensor && inp->device_input_tensor < 3 && inp->bit_depth_luma != 8) { snprintf(err, errlen, "DeviceInputTensor=%d holds 8-bit components: it needs SourceBitDepthLuma=8 (got %d)", inp->device_input_tensor, inp->bit_depth_luma); return -1; }
+    if (inp->device_input_tensor == 3 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputTensor=3 (gbrp10le) holds 10-bit components: it needs SourceBitDepthLuma=10 (got %d)", inp->bit_depth_luma); return -1; }
+    if (inp->device_input_tensor == 4 && inp->bit_depth_luma != 8 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputTensor=4 (gbrpf32le) is quantised to 8 or 10 bits: it needs SourceBitDepthLuma=8 or 10 (got %d)", inp->bit_depth_luma); return -1; }
+    if (inp->device_input_tensor && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV (InputFile=%s)", inp->device_input_tensor, inp->infile); return -1; }
+    if (inp->device_input_tensor && !inp->device_writer_async) { snprintf(err, errlen, "DeviceInputTensor=%d leaves no YUV source on the host, so the distortion comes from the device's SSDs: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1)", inp->device_input_tensor); return -1; }
     if (inp->symbol_mode && inp->profile_idc == 66) { snprintf(err, errlen, "SymbolMode=1 (CABAC) is not allowed in the Baseline profile (ProfileIDC=66)"); return -1; }
     if (inp->symbol_mode && inp->context_init_method) { snprintf(err, errlen, "ContextInitMethod=1 (adaptive CABAC model selection) not supported (0: FixedModelNumber)"); return -1; }
     if (inp->symbol_mode && inp->model_number) { snprintf(err, errlen, "FixedModelNumber=%d not supported (0: cabac_init_idc 0)", inp->model_number); return -1; }

@@ -437,6 +437,17 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fprintf(stderr, "DeviceInputFormat=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n", inp->device_input_format);
         return JMH_E_UNSUPPORTED_CFG;
     }
+    const int tensor_kind = inp->device_input_tensor;
+    const int tensor_flags = (inp->device_input_matrix ? JMH_PIX_BT709 : 0) | (inp->device_input_full ? JMH_PIX_FULL_RANGE : 0);
+    const jm_device_push_tensor_fn device_input_tensor_fn = tensor_kind ? jm_device_input_tensor() : NULL;
+    if (tensor_kind && (rgb_format || !device_input_fn || !device_input_tensor_fn)) {
+        fprintf(stderr, "DeviceInputTensor=%d needs DeviceInput=1 on the device backend and DeviceInputFormat=0 (backend '%s')\n", tensor_kind, be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
+    if (tensor_kind && !inp->device_writer_async) {
+        fprintf(stderr, "DeviceInputTensor=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n", tensor_kind);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     if (inp->device_writer_async && !(device_coded_push_fn && device_coded_pop_fn)) {
         fprintf(stderr, "DeviceWriterAsync=1 needs the device backend (backend '%s' has no coded push / pop: DeviceWriterAsync=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
@@ -467,6 +478,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     uint64_t seed = 0;
     int synthetic = !strncmp(inp->infile, "synthetic:", 10);
     if (synthetic && rgb_format) { fprintf(stderr, "DeviceInputFormat=%d reads RGB frames from InputFile: the synthetic source is YUV\n", inp->device_input_format); return JMH_E_UNSUPPORTED_CFG; }
+    if (synthetic && tensor_kind) { fprintf(stderr, "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV\n", tensor_kind); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic) seed = strtoull(inp->infile + 10, NULL, 10);
     else if (!(fin = fopen(inp->infile, "rb"))) { fprintf(stderr, "Input file %s does not exist\n", inp->infile); return JMH_E_INVALID_ARG; }
     if (!(fout = fopen(inp->outfile, "wb"))) { fprintf(stderr, "Cannot open output file %s\n", inp->outfile); if (fin) fclose(fin); return JMH_E_INVALID_ARG; }
@@ -495,10 +507,12 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     pend_t *pend = (pend_t *)calloc(plen, sizeof(pend_t));
     jm_pic rec;
     memset(&rec, 0, sizeof(rec));
-    /* DeviceInputFormat: one frame as read, height rows of 4 * width bytes (free again when its upload returns) */
-    const size_t rgb_bytes = (size_t)4 * inp->width * inp->height;
-    uint8_t *rgb = rgb_format ? (uint8_t *)malloc(rgb_bytes) : NULL;
-    int alloc_fail = !pend || (rgb_format && !rgb) || jm_pic_alloc_bd(&rec, W, H, bd);
+    /* DeviceInputFormat: one frame as read, height rows of 4 * width bytes (free again when its upload returns);
+       DeviceInputTensor: one frame of its file, in the same buffer */
+    const int raw_source = rgb_format || tensor_kind;
+    const size_t rgb_bytes = tensor_kind ? jm_tensor_frame_bytes(tensor_kind, inp->width, inp->height) : (size_t)4 * inp->width * inp->height;
+    uint8_t *rgb = raw_source ? (uint8_t *)malloc(rgb_bytes) : NULL;
+    int alloc_fail = !pend || (raw_source && !rgb) || jm_pic_alloc_bd(&rec, W, H, bd);
     for (int k = 0; k < plen && !alloc_fail; k++) alloc_fail = jm_pic_alloc_bd(&pend[k].cur, W, H, bd);
     if (alloc_fail) {
         if (pend) for (int k = 0; k < plen; k++) jm_pic_free(&pend[k].cur);
@@ -574,6 +588,10 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         if (rgb_format)
             fprintf(log, " (the source is RGB, format %d: converted on the device with the BT.%s matrix at %s range; the stream does not signal either)\n",
                     inp->device_input_format, inp->device_input_matrix ? "709" : "601", inp->device_input_full ? "full" : "limited");
+        if (tensor_kind)
+            fprintf(log, " (the source is an RGB tensor, %s: quantised and converted on the device with the BT.%s matrix at %s range; the stream does not signal either)\n",
+                    tensor_kind == 1 ? "rgb24" : tensor_kind == 2 ? "gbrp" : tensor_kind == 3 ? "gbrp10le" : "gbrpf32le",
+                    inp->device_input_matrix ? "709" : "601", inp->device_input_full ? "full" : "limited");
         if (device_input_fn) fprintf(log, " (the source is uploaded as read and pushed from device memory: the device pads it to the coded size)\n");
         if (async) fprintf(log, " (the slice writer is queued behind each picture: its pop returns the slice bytes and the SSDs)\n");
         if (nal) fprintf(log, " (NAL units finished on the device: the pop returns the picture's access unit)\n");
@@ -726,7 +744,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         pend_t *p = &pend[(head + count) % plen];
         int idx = inp->start_frame + f;
         double tr = now_ms();
-        if (rgb_format) {
+        if (raw_source) {
             if (fseek(fin, (long)rgb_bytes * idx, SEEK_SET) || fread(rgb, 1, rgb_bytes, fin) != rgb_bytes) { fprintf(stderr, "ReadOneFrame: cannot read RGB frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
         } else
         if (synthetic) jm_synth_frame(&p->cur, inp->width, inp->height, seed, idx);
@@ -757,7 +775,8 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             PEND_SLICE(p, sl);
             device_slice_headers(d, &s, &sl);
             if (nal && !(r = device_slice_heads(d, &sl))) r = device_nal_fn(be->ctx, d->n, d->nh);
-            if (!r) r = rgb_format ? device_input_rgb_fn(be->ctx, rgb, rgb_format, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
+            if (!r) r = tensor_kind ? device_input_tensor_fn(be->ctx, rgb, tensor_kind, tensor_flags, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
+                  : rgb_format ? device_input_rgb_fn(be->ctx, rgb, rgb_format, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
                   : device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
                                 : device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
         } else

@@ -94,6 +94,12 @@ typedef struct jm_input {
                                   Needs DeviceWriterAsync 1 (the distortion comes from the device's SSDs) */
     int  device_input_matrix;  /* (this build) DeviceInputMatrix 1: BT.709 (0: BT.601); RGB formats only        */
     int  device_input_full;    /* (this build) DeviceInputFullRange 1: full range (0: limited); RGB formats only */
+    int  device_input_tensor;  /* (this build) DeviceInputTensor 1..4: with DeviceInput 1 InputFile holds RGB frames as
+                                  ffmpeg -pix_fmt writes them: 1 rgb24 (HWC u8), 2 gbrp (three u8 planes G, B, R),
+                                  3 gbrp10le (three u16 planes; SourceBitDepthLuma 10), 4 gbrpf32le (three float32
+                                  planes; 8- or 10-bit).  A frame is uploaded raw and pushed as a device tensor
+                                  (include/jmhip_tensor.h); DeviceInputMatrix / DeviceInputFullRange apply.  0: off.
+                                  Needs DeviceWriterAsync 1; excludes DeviceInputFormat                      */
     int  device_nal;           /* (this build) DeviceNAL 1: with DeviceWriterAsync 1 the NAL units are finished
                                   on the device behind the slice writer (jmh_coded_nal_heads): the pop
                                   returns the picture's Annex B access unit, appended to the stream in
@@ -285,6 +291,15 @@ typedef int (*jm_device_push_rgb_fn)(void *ctx, const void *rgb, int format, int
                                      const jmh_coded_slice *slices, int crop_w, int crop_h);
 void jm_set_device_input_rgb(jm_device_push_rgb_fn fn);
 jm_device_push_rgb_fn jm_device_input_rgb(void);
+/* DeviceInputTensor 1..4: the backend's push of a frame as a device tensor (jmh_frame_push_coded_tensor).
+   frame holds jm_tensor_frame_bytes(kind, disp_w, disp_h) bytes as read; flags: JMH_PIX_BT709 | JMH_PIX_FULL_RANGE */
+typedef int (*jm_device_push_tensor_fn)(void *ctx, const void *frame, int kind, int flags, int disp_w, int disp_h, const jmh_frame_params *fp,
+                                        int n, const jmh_coded_slice *slices, int crop_w, int crop_h);
+void jm_set_device_input_tensor(jm_device_push_tensor_fn fn);
+jm_device_push_tensor_fn jm_device_input_tensor(void);
+/* bytes of an element and of a frame of a DeviceInputTensor file */
+static inline int jm_tensor_elem_bytes(int kind) { return kind == 4 ? 4 : kind == 3 ? 2 : 1; }
+static inline size_t jm_tensor_frame_bytes(int kind, int w, int h) { return (size_t)3 * jm_tensor_elem_bytes(kind) * w * h; }
 /* 10 log10(peak^2 w h / ssd) with psnr_pl's arithmetic (99.0 at ssd 0): the PSNR of a w x h plane of
    bit_depth-bit samples from its summed squared error */
 double jm_psnr_from_ssd(uint64_t ssd, int w, int h, int bit_depth);

@@ -103,6 +103,34 @@ static int gpu_push_device_rgb(void *ctx, const void *rgb, int format, int dw, i
     pic.stream = gpu_in.stream;
     return jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch);
 }
+/* DeviceInputTensor 1..4: the frame as read (rgb24, gbrp, gbrp10le, gbrpf32le), through the same buffer and
+   stream, described as a device tensor; the device quantises and converts it */
+static int gpu_push_device_tensor(void *ctx, const void *frame, int kind, int flags, int dw, int dh, const jmh_frame_params *fp, int n,
+                                  const jmh_coded_slice *sl, int cw, int ch) {
+    const size_t bytes = jm_tensor_frame_bytes(kind, dw, dh), es = (size_t)jm_tensor_elem_bytes(kind), plane = es * dw * dh;
+    int r;
+    if (!gpu_in.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_in.stream))) return r;
+    if (gpu_in.bytes < bytes) {
+        if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_in.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_in.buf))) return r;
+        gpu_in.bytes = bytes;
+    }
+    if ((r = jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, frame, bytes, gpu_in.stream))) return r;
+    const uint8_t *base = (const uint8_t *)gpu_in.buf;
+    jmh_device_tensor t;
+    memset(&t, 0, sizeof(t));
+    t.dtype = kind == 4 ? JMH_T_F32 : kind == 3 ? JMH_T_U16 : JMH_T_U8;
+    t.flags = flags;
+    t.width = dw; t.height = dh;
+    if (kind == 1) {   /* rgb24: pixels of R, G, B */
+        t.chan[0] = base; t.chan[1] = base + 1; t.chan[2] = base + 2;
+        t.stride_x = 3; t.stride_y = (int64_t)3 * dw;
+    } else {           /* gbrp*: planes G, B, R */
+        t.chan[0] = base + 2 * plane; t.chan[1] = base; t.chan[2] = base + plane;
+        t.stride_x = (int64_t)es; t.stride_y = (int64_t)es * dw;
+    }
+    t.stream = gpu_in.stream;
+    return jmh_frame_push_coded_tensor((jmh_ctx *)ctx, &t, fp, n, sl, cw, ch);
+}
 static void gpu_input_release(void *ctx) {
     if (gpu_in.stream) (void)jmh_device_stream_destroy((jmh_ctx *)ctx, gpu_in.stream);
     if (gpu_in.buf) (void)jmh_device_free((jmh_ctx *)ctx, gpu_in.buf);
@@ -115,6 +143,7 @@ int main(int argc, char **argv) {
     jm_input_defaults(&inp);
     jm_set_device_input(gpu_push_device);   /* before PatchInp: it rejects DeviceInput on a backend without one */
     jm_set_device_input_rgb(gpu_push_device_rgb);
+    jm_set_device_input_tensor(gpu_push_device_tensor);
     if (jm_configure(&inp, argc, argv, err, sizeof(err))) { fprintf(stderr, "%s\n", err); return 1; }
     jmh_config cfg;
     jm_fill_config(&inp, &cfg);

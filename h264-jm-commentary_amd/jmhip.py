@@ -294,6 +294,24 @@ _SIGS_RGB = {
 }
 EXPORTED_RGB = list(_SIGS_RGB)
 
+# ---- RGB tensors pushed from the device (include/jmhip_tensor.h; additive to ABI 14) ----
+JMH_T_U8, JMH_T_U16, JMH_T_F16, JMH_T_BF16, JMH_T_F32 = 0, 1, 2, 3, 4
+TENSOR_ELEM_BYTES = {JMH_T_U8: 1, JMH_T_U16: 2, JMH_T_F16: 2, JMH_T_BF16: 2, JMH_T_F32: 4}
+
+
+class JmhDeviceTensor(ctypes.Structure):
+    _fields_ = [("dtype", ctypes.c_int32), ("flags", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("chan", ctypes.c_void_p * 3), ("stride_x", ctypes.c_int64), ("stride_y", ctypes.c_int64), ("stream", ctypes.c_void_p)]
+
+
+_SIGS_TENSOR = {
+    "jmh_frame_push_tensor": (_I, [_P, _P, ctypes.POINTER(JmhFrameParams)]),
+    "jmh_frame_push_coded_tensor": (_I, [_P, _P, ctypes.POINTER(JmhFrameParams), _I, _P, _I, _I]),
+    "jmh_ingest_tensor": (_I, [_P, _P, _P, _P, _P, _I, _I]),
+    "jmh_tensor_quantise": (_I, [_I, _I, _P, ctypes.c_size_t, _P]),
+}
+EXPORTED_TENSOR = list(_SIGS_TENSOR)
+
 # ---- the unit seam of the searches' spiral decode (include/jmhip_spiral.h; additive to ABI 14);
 #      bound where it is called (Encoder.spiral_positions), so that a library built before it loads
 _SIGS_SPIRAL = {
@@ -308,6 +326,30 @@ def rgb_coefficients(format, bit_depth):
     out = (ctypes.c_int32 * 12)()
     _check(load().jmh_rgb_coefficients(format, bit_depth, out), "jmh_rgb_coefficients")
     return [int(v) for v in out]
+
+
+def _tensor_dtype(a, dtype=None):
+    """The JMH_T_* of a numpy array: from its dtype, unless given (bfloat16 travels as its uint16 bits)."""
+    if dtype is not None:
+        if a.dtype.itemsize != TENSOR_ELEM_BYTES[dtype]:
+            raise ValueError(f"elements of {a.dtype.itemsize} bytes do not hold dtype {dtype}")
+        return dtype
+    for np_dt, t in ((np.uint8, JMH_T_U8), (np.uint16, JMH_T_U16), (np.float16, JMH_T_F16), (np.float32, JMH_T_F32)):
+        if a.dtype == np_dt:
+            return t
+    raise ValueError(f"no tensor dtype for numpy {a.dtype} (uint8, uint16, float16, float32; bfloat16 as uint16 bits with dtype=JMH_T_BF16)")
+
+
+def tensor_quantise(array_or_bits, dtype, bit_depth):
+    """jmh_tensor_quantise: the integer components in [0, 2^bit_depth - 1] of the elements of a numpy
+    array (any shape; a float16 / float32 array, or the elements' bits as uint16 / uint32, which is how
+    bfloat16 travels), as int32 of the same shape.  Needs no device."""
+    a = np.ascontiguousarray(array_or_bits)
+    if a.dtype.itemsize != TENSOR_ELEM_BYTES.get(dtype, a.dtype.itemsize):
+        raise ValueError(f"elements of {a.dtype.itemsize} bytes do not hold dtype {dtype}")
+    q = np.empty(a.shape, np.int32)
+    _check(load().jmh_tensor_quantise(dtype, bit_depth, _ptr(a), a.size, _ptr(q)), "jmh_tensor_quantise")
+    return q
 
 
 def nal_geometry():
@@ -331,8 +373,8 @@ def nal_heads(heads):
 
 
 def _addr(p):
-    """A device address: an int, or any object with data_ptr() (a torch tensor, for one; that
-    interoperation is not tested: the tests here do not load a second HIP runtime)."""
+    """A device address: an int, or any object with data_ptr() (a torch tensor, for one; for a whole
+    descriptor of one, with its stream, see Encoder.from_torch)."""
     return int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)
 
 
@@ -420,6 +462,82 @@ def to_device_rgb(array, format, pad_stride=0, misalign=0):
     return HostLayout(format, w, h, buf, [misalign], [stride])
 
 
+class DeviceTensor:
+    """jmh_device_tensor over addresses you own: dtype (JMH_T_*), flags (JMH_PIX_BT709 |
+    JMH_PIX_FULL_RANGE), the size in pixels, the device addresses of R, G and B at pixel (0, 0) (ints or
+    objects with data_ptr()), the bytes between pixels and between rows, and the stream on which the
+    elements are complete (or None)."""
+
+    def __init__(self, dtype, flags, width, height, chans, stride_x, stride_y, stream=None):
+        self.dtype, self.flags, self.width, self.height = dtype, flags, width, height
+        self.chans, self.stride_x, self.stride_y, self.stream = list(chans), stride_x, stride_y, stream
+
+    def struct(self):
+        s = JmhDeviceTensor(self.dtype, self.flags, self.width, self.height)
+        for i, p in enumerate(self.chans):
+            s.chan[i] = _addr(p) if p is not None else None
+        s.stride_x, s.stride_y, s.stream = self.stride_x, self.stride_y, self.stream
+        return s
+
+
+class TensorLayout:
+    """What to_device_tensor lays out: buf (uint8, to be uploaded as one block), the byte offsets of
+    R, G and B at pixel (0, 0) in it, and the two strides."""
+
+    def __init__(self, dtype, flags, width, height, buf, offsets, stride_x, stride_y):
+        self.dtype, self.flags, self.width, self.height = dtype, flags, width, height
+        self.buf, self.offsets, self.stride_x, self.stride_y = buf, offsets, stride_x, stride_y
+
+    def at(self, base, stream=None):
+        """The DeviceTensor of this layout uploaded at device address base."""
+        return DeviceTensor(self.dtype, self.flags, self.width, self.height, [_addr(base) + o for o in self.offsets], self.stride_x,
+                            self.stride_y, stream)
+
+
+def to_device_tensor(array, layout="chw", order="rgb", flags=0, pad_stride=0, misalign=0, dtype=None):
+    """An RGB tensor laid out as a TensorLayout.  array: (C, h, w) for layout "chw" with C = 3, or
+    (h, w, C) for "hwc" with C = 3 or 4, of uint8, uint16, float16 or float32 (bfloat16: its uint16
+    bits with dtype=JMH_T_BF16).  order: which channel of the array is which component, "rgb",
+    "bgr", "gbr", ... (a fourth channel of "hwc" is never read).  pad_stride: bytes added to every row
+    (a multiple of the element size, filled with 0xA5); misalign: the offset in bytes of every
+    channel's base from a 256-byte boundary of the block (a multiple of the element size).  Nothing
+    lies behind the last element read of the last row."""
+    a = np.ascontiguousarray(array)
+    dt = _tensor_dtype(a, dtype)
+    es = TENSOR_ELEM_BYTES[dt]
+    if a.ndim != 3 or layout not in ("chw", "hwc") or sorted(order) != ["b", "g", "r"]:
+        raise ValueError("to_device_tensor takes a 3-D array, layout 'chw' or 'hwc' and an order that is a permutation of 'rgb'")
+    if misalign % es or pad_stride % es:
+        raise ValueError("misalign and pad_stride are multiples of the element size")
+    where = [order.index(c) for c in "rgb"]                   # the array's channel of R, G, B
+    raw = a.view(np.uint8)
+    if layout == "chw":
+        C, h, w = a.shape
+        if C != 3:
+            raise ValueError("layout 'chw' takes (3, h, w)")
+        rb = w * es
+        stride_y = rb + pad_stride
+        starts, end = [], 0
+        for _ in range(3):
+            starts.append((end + 255) // 256 * 256 + misalign)
+            end = starts[-1] + (h - 1) * stride_y + rb          # no byte behind the last row's elements
+        buf = np.full(end, 0xA5, np.uint8)
+        for c in range(3):
+            rows = np.lib.stride_tricks.as_strided(buf[starts[c]:], (h, rb), (stride_y, 1))
+            rows[:] = raw[c].reshape(h, rb)
+        return TensorLayout(dt, flags, w, h, buf, [starts[c] for c in where], es, stride_y)
+    h, w, C = a.shape
+    if C not in (3, 4):
+        raise ValueError("layout 'hwc' takes (h, w, 3) or (h, w, 4)")
+    rb = w * C * es
+    stride_y = rb + pad_stride
+    end = misalign + (h - 1) * stride_y + ((w - 1) * C + 3) * es   # the last pixel's three channels, not its fourth
+    buf = np.full(misalign + (h - 1) * stride_y + rb, 0xA5, np.uint8)
+    rows = np.lib.stride_tricks.as_strided(buf[misalign:], (h, rb), (stride_y, 1))
+    rows[:] = raw.reshape(h, rb)
+    return TensorLayout(dt, flags, w, h, buf[:end].copy(), [misalign + c * es for c in where], C * es, stride_y)
+
+
 def pad_to_coded(pics, cw, ch):
     """host/yuv.c jm_pad_picture in numpy: (y, u, v) of the source size replicated to cw x ch."""
     out = []
@@ -474,7 +592,7 @@ def load(path=LIB_PATH):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()) + \
-            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()) + list(_SIGS_NAL.items()) + list(_SIGS_RGB.items()):
+            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()) + list(_SIGS_NAL.items()) + list(_SIGS_RGB.items()) + list(_SIGS_TENSOR.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -483,6 +601,19 @@ def load(path=LIB_PATH):
     if path == LIB_PATH:
         _lib = lib
     return lib
+
+
+def _one_hip_runtime():
+    """Stream handles and events belong to one HIP runtime.  A process that loaded this library before
+    torch can hold two (torch brings its own copy): refuse to pass handles between them."""
+    try:
+        with open("/proc/self/maps") as f:
+            paths = {line.split()[-1] for line in f if "libamdhip64" in line}
+    except OSError:
+        return
+    if len(paths) > 1:
+        raise JmhError("two HIP runtimes in this process (" + ", ".join(sorted(paths)) + "): a torch stream cannot be handed to libjmhip.so; "
+                       "import torch before jmhip loads its library")
 
 
 def _check(st, what):
@@ -750,6 +881,80 @@ class Encoder:
         v = np.empty_like(u)
         s = pic.struct()
         _check(self.lib.jmh_ingest_picture(self.ctx, ctypes.byref(s), _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2), "jmh_ingest_picture")
+        return y, u, v
+
+    # ---- tensors that are already on the device (include/jmhip_tensor.h) ----
+    def device_tensor(self, layout, stream=None, base=None):
+        """A TensorLayout (to_device_tensor) uploaded: into base, or into a new allocation of exactly
+        its bytes (the caller frees .base).  Returns the DeviceTensor."""
+        if base is None:
+            base = self.device_alloc(layout.buf.nbytes)
+        self.device_upload(base, layout.buf, stream)
+        t = layout.at(base, stream)
+        t.base = base
+        return t
+
+    def from_torch(self, t, layout=None, order="rgb", flags=0, stream=None):
+        """The DeviceTensor of a torch tensor on this context's device, with no copy: addresses from
+        data_ptr(), strides from stride(), the element type from dtype (uint8, uint16, float16,
+        bfloat16, float32).  layout "chw" or "hwc"; None infers it for a 3-D tensor whose first or
+        last dimension is 3 or 4 (the last wins when both are).  Views are fine (permute, slices,
+        crops) while the strides stay positive.  stream: the stream handle on which t is complete;
+        None takes the stream torch is currently queueing on for t's device, and where that is the
+        null stream, which cannot be ordered against, synchronises it.  Keep t alive, and do not
+        write to it outside that stream, until input_wait() or the picture's pop.  torch must share
+        this library's HIP runtime: import torch before the first Encoder is made."""
+        import torch                                           # not at module load
+        types = {torch.uint8: JMH_T_U8, torch.float16: JMH_T_F16, torch.bfloat16: JMH_T_BF16, torch.float32: JMH_T_F32}
+        if hasattr(torch, "uint16"):
+            types[torch.uint16] = JMH_T_U16
+        if t.dtype not in types:
+            raise ValueError(f"from_torch: no tensor dtype for {t.dtype}")
+        if not t.is_cuda or t.dim() != 3:
+            raise ValueError("from_torch takes a 3-D tensor on the device")
+        _one_hip_runtime()
+        if layout is None:
+            layout = "hwc" if t.shape[2] in (3, 4) else "chw" if t.shape[0] in (3, 4) else None
+        if layout not in ("chw", "hwc") or sorted(order) != ["b", "g", "r"]:
+            raise ValueError("from_torch: layout is 'chw' or 'hwc' (not inferable from this shape) and order a permutation of 'rgb'")
+        es = t.element_size()
+        sc, sy, sx = (t.stride(i) * es for i in ((0, 1, 2) if layout == "chw" else (2, 0, 1)))
+        h, w = (t.shape[1], t.shape[2]) if layout == "chw" else (t.shape[0], t.shape[1])
+        if t.shape[0 if layout == "chw" else 2] < 3:
+            raise ValueError("from_torch: fewer than three channels")
+        if stream is None:
+            cur = torch.cuda.current_stream(t.device)
+            stream = cur.cuda_stream or None
+            if stream is None:
+                cur.synchronize()
+        base = t.data_ptr()
+        return DeviceTensor(types[t.dtype], flags, w, h, [base + order.index(c) * sc for c in "rgb"], sx, sy, stream)
+
+    def push_tensor(self, t, slice_type, qp, chroma_qp_offset=0, deblock=None):
+        """jmh_frame_push_tensor: push() of a DeviceTensor; the library quantises, converts and pads it."""
+        fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
+        s = t.struct()
+        _check(self.lib.jmh_frame_push_tensor(self.ctx, ctypes.byref(s), ctypes.byref(fp)), "jmh_frame_push_tensor")
+
+    def push_coded_tensor(self, t, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0, heads=None):
+        """jmh_frame_push_coded_tensor: push_coded() of a DeviceTensor."""
+        self._arm(heads)
+        fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
+        cw, ch = crop if crop is not None else (self.w, self.h)
+        self._coded_n = getattr(self, "_coded_n", [])
+        s = t.struct()
+        _check(self.lib.jmh_frame_push_coded_tensor(self.ctx, ctypes.byref(s), ctypes.byref(fp), len(descs), ctypes.cast(descs, _P), cw, ch),
+               "jmh_frame_push_coded_tensor")
+        self._coded_n.append(len(descs))
+
+    def ingest_tensor(self, t):
+        """jmh_ingest_tensor, the unit seam: the DeviceTensor quantised, converted, packed and padded
+        by the kernel, as (y, u, v) of the coded size."""
+        y = np.empty((self.h, self.w), self.pdt)
+        u = np.empty((self.h // 2, self.w // 2), self.pdt)
+        v = np.empty_like(u)
+        s = t.struct()
+        _check(self.lib.jmh_ingest_tensor(self.ctx, ctypes.byref(s), _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2), "jmh_ingest_tensor")
         return y, u, v
 
     def input_wait(self):

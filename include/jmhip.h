@@ -386,5 +386,6 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #include "jmhip_input.h"
 #include "jmhip_nal.h"
 #include "jmhip_rgb.h"
+#include "jmhip_tensor.h"
 #include "jmhip_spiral.h"
 #endif /* JMHIP_H */
