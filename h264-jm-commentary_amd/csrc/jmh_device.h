@@ -5,6 +5,7 @@
 #include "../../include/jmhip.h"
 #include "jmh_rgb.h"
 #include "jmh_tensor.h"
+#include "jmh_output.h"
 
 #define SRMAX 32                         // LDS-resident FFS window: SearchRange <= 32
 #define SIDE_MAX (2 * SRMAX + 1)
@@ -298,6 +299,15 @@ struct TensorArgs {
     uint8_t *dst;                        // Y, U, V of the coded size, samples of 1 or 2 bytes
     int w, h, W, H;
     jmr_coef k;                          // the conversion of the flags at the context's bit depth (maxv: M of the quantiser)
+};
+
+// k_pull_picture / k_pull_tensor (jmh_output.hip): the w x h crop of a packed W x H picture written into the caller's memory
+struct OutArgs {
+    const uint8_t *src;                  // Y, U, V of the coded size, samples of 1 or 2 bytes (k.maxv > 255: 2)
+    uint8_t *dst[3];                     // planes of the caller (jmhip_output.h) / R, G, B of its tensor at pixel (0, 0)
+    int64_t stride[3];                   // a picture: bytes per row of each plane; a tensor: stride_x, stride_y
+    int w, h, W, H;
+    jmout_coef k;                        // the conversion of the flags at the context's bit depth (a YUV format: maxv only)
 };
 
 // The stores of the converting ingest kernels (k_ingest_rgb, k_ingest_tensor): 8 luma samples of a row or 4 + 4

@@ -16,6 +16,8 @@ size_t jmh_rdo_scratch_bytes();
 hipError_t jmh_launch_ingest(int format, const IngestArgs &a, hipStream_t st);      // jmh_ingest.hip
 hipError_t jmh_launch_ingest_rgb(int format, const RgbArgs &a, hipStream_t st);    // jmh_rgb.hip
 hipError_t jmh_launch_ingest_tensor(int dtype, const TensorArgs &a, hipStream_t st);   // jmh_tensor.hip
+hipError_t jmh_launch_pull_picture(int format, const OutArgs &a, hipStream_t st);      // jmh_output.hip
+hipError_t jmh_launch_pull_tensor(int dtype, const OutArgs &a, hipStream_t st);
 
 // the unit seams: pel = uint8_t or uint16_t samples (instantiated for both where they are defined);
 // qpb = qp + QpBdOffset, maxv = (1 << bit depth) - 1 (8 bits: qp and 255)

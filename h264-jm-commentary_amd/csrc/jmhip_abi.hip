@@ -26,6 +26,7 @@
 #include "jmh_ingest.h"
 #include "jmh_rgb.h"
 #include "jmh_tensor.h"
+#include "jmh_output.h"
 #include "jmh_nal.h"
 #include "jmh_spiral.h"
 
@@ -149,6 +150,8 @@ struct PicBuf {
     // device pictures (jmhip_input.h)
     int dev_fmt;                         // the occupant was pushed as a device picture: its format + 1, else 0 (a host picture, a tensor)
     hipEvent_t ev_in;                    //   the caller's stream at the push (created on first use)
+    // pulled pictures (jmhip_output.h)
+    hipEvent_t ev_out;                   // the last pull that read rec / dbk (created on first use); the next claim waits for it
 };
 
 // offsets into PicBuf::cd_h / cd_d (each a multiple of 8)
@@ -264,6 +267,7 @@ struct jmh_ctx {
     uint8_t *up_h = nullptr;             // jmh_device_upload on a stream: its pinned buffer,
     size_t up_cap = 0;
     hipEvent_t ev_up = nullptr;          //   the last copy out of it
+    hipStream_t ost = nullptr;           // pulls without a caller's stream, the convert seams, downloads (created on first use)
 };
 
 #define HCHK(x)                                                                  \
@@ -305,7 +309,7 @@ static void free_entry(PicBuf &b) {
     for (void *p : dev_bufs) if (p) (void)hipFree(p);
     void *host_bufs[] = {b.h_res, b.h_src, b.h_rec, b.h_dbk, b.h_rp, b.cd_h, b.nal.h};
     for (void *p : host_bufs) if (p) (void)hipHostFree(p);
-    hipEvent_t evs[] = {b.ev_src, b.ev_t0, b.ev_done, b.ev_fin, b.ev_rp, b.ev_in};
+    hipEvent_t evs[] = {b.ev_src, b.ev_t0, b.ev_done, b.ev_fin, b.ev_rp, b.ev_in, b.ev_out};
     for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
 }
 
@@ -416,6 +420,13 @@ static int rdo_schedule(jmh_ctx *c, std::vector<int> &order, std::vector<int> &o
     return 0;
 }
 
+// the host waits for every pull queued so far (jmh_device_output_wait)
+static int output_wait(jmh_ctx *c) {
+    for (PicBuf &b : c->ring)
+        if (b.ev_out) HCHK(hipEventSynchronize(b.ev_out));
+    return JMH_OK;
+}
+
 extern "C" {
 
 void jmh_destroy(jmh_ctx *c) {
@@ -424,6 +435,8 @@ void jmh_destroy(jmh_ctx *c) {
     if (c->st) (void)hipStreamSynchronize(c->st);
     if (c->cst) (void)hipStreamSynchronize(c->cst);
     if (c->sst) (void)hipStreamSynchronize(c->sst);
+    (void)output_wait(c);
+    if (c->ost) (void)hipStreamDestroy(c->ost);
     jmh_cavlc_free(c->cavlc);
     jmh_cabac_free(c->cabac);
     for (PicBuf &b : c->ring) free_entry(b);
@@ -1034,7 +1047,8 @@ static int issue_while(jmh_ctx *c, Cond cond) {
 
 static int drain(jmh_ctx *c) {
     int r = issue_while(c, [c] { return !c->fl.empty(); });
-    return r ? r : flow_flush(c);
+    if (!r) r = flow_flush(c);
+    return r ? r : output_wait(c);
 }
 
 static const uint8_t *ref_ptr(const jmh_ctx *c) {
@@ -1139,6 +1153,8 @@ static int claim_entry(jmh_ctx *c, int *out) {
         c->ref_kind = REF_BUF;
         c->ref_entry = -1;
     }
+    // the entry's last pull (jmhip_output.h) reads rec / dbk: what rewrites them is queued behind it
+    if (c->ring[e].ev_out) HCHK(hipStreamWaitEvent(c->st, c->ring[e].ev_out, 0));
     c->next_entry = (e + 1) % c->nring;
     *out = e;
     return JMH_OK;
@@ -1831,6 +1847,141 @@ extern "C" int jmh_tensor_quantise(int dtype, int bit_depth, const void *elems, 
     for (size_t i = 0; i < n; i++) q[i] = jmt_quant(dtype, jmt_load(dtype, p + i * jmt_es(dtype)), M);
     return JMH_OK;
 }
+
+// ---- decoded pictures pulled on the device (include/jmhip_output.h) ----
+// the destination of a pull: a picture or a tensor
+struct PullDst { const jmh_device_picture_out *pic; const jmh_device_tensor_out *ten; };
+
+// the argument rules, then the context's bit depth
+static int check_pull_dst(const jmh_ctx *c, const PullDst &d) {
+    if (d.pic) {
+        const jmh_device_picture_out *p = d.pic;
+        if (jmout_check_picture(p->format, p->width, p->height, c->W, c->H, p->plane, p->stride)) return JMH_E_INVALID_ARG;
+        return jmout_picture_depth_ok(p->format, c->bd) ? JMH_OK : JMH_E_UNSUPPORTED_CFG;
+    }
+    const jmh_device_tensor_out *t = d.ten;
+    if (!t || jmout_check_tensor(t->dtype, t->flags, t->width, t->height, c->W, c->H, t->chan, t->stride_x, t->stride_y)) return JMH_E_INVALID_ARG;
+    return jmout_tensor_depth_ok(t->dtype, c->bd) ? JMH_OK : JMH_E_UNSUPPORTED_CFG;
+}
+static int output_stream(jmh_ctx *c) {
+    if (!c->ost && hipStreamCreateWithFlags(&c->ost, hipStreamNonBlocking) != hipSuccess) { c->ost = nullptr; return JMH_E_HIP; }
+    return JMH_OK;
+}
+// the one kernel of a (checked) destination, reading the packed picture at src, on st
+static int pull_launch(jmh_ctx *c, const PullDst &d, const uint8_t *src, hipStream_t st) {
+    OutArgs a;
+    a.src = src; a.W = c->W; a.H = c->H;
+    if (d.pic) {
+        const jmh_device_picture_out *p = d.pic;
+        for (int i = 0; i < 3; i++) { a.dst[i] = (uint8_t *)p->plane[i]; a.stride[i] = p->stride[i]; }
+        a.w = p->width; a.h = p->height;
+        jmout_coefficients(p->format, c->bd, &a.k);   // a YUV format reads none of them
+        HCHK(jmh_launch_pull_picture(p->format, a, st));
+    } else {
+        const jmh_device_tensor_out *t = d.ten;
+        for (int i = 0; i < 3; i++) a.dst[i] = (uint8_t *)t->chan[i];
+        a.stride[0] = t->stride_x; a.stride[1] = t->stride_y; a.stride[2] = 0;
+        a.w = t->width; a.h = t->height;
+        jmout_coefficients(t->flags, c->bd, &a.k);
+        HCHK(jmh_launch_pull_tensor(t->dtype, a, st));
+    }
+    return JMH_OK;
+}
+// jmh_pull_picture / jmh_pull_tensor.  The current picture is complete (its pop waited for it), so the
+// kernel waits for nothing but its stream: the caller's, where it is ordered behind the destination's
+// last consumer and in front of its next one, or the context's own, waited for here.  The entry's
+// event then holds the pull, for the claim that rewrites the entry (claim_entry) and for output_wait;
+// an earlier pull of the entry on another stream is chained in front, so one event holds them all.
+static int pull_any(jmh_ctx *c, int which, const PullDst &d, void *stream) {
+    if (which != JMOUT_DEBLOCKED && which != JMOUT_RECON) return JMH_E_INVALID_ARG;
+    int r = check_pull_dst(c, d);
+    if (r) return r;
+    if (c->cur_entry < 0) return JMH_E_STATE;
+    PicBuf &b = c->ring[c->cur_entry];
+    if (which == JMOUT_DEBLOCKED && !b.deblocked) return JMH_E_STATE;
+    HCHK(hipSetDevice(c->dev));
+    hipStream_t st = (hipStream_t)stream;
+    if (!st) { if ((r = output_stream(c))) return r; st = c->ost; }
+    if (b.ev_out) HCHK(hipStreamWaitEvent(st, b.ev_out, 0));
+    else if (hipEventCreateWithFlags(&b.ev_out, hipEventDisableTiming) != hipSuccess) { b.ev_out = nullptr; return JMH_E_HIP; }
+    if ((r = pull_launch(c, d, which == JMOUT_DEBLOCKED ? b.dbk : b.rec, st))) return r;
+    HCHK(hipEventRecord(b.ev_out, st));
+    if (!stream) HCHK(hipStreamSynchronize(st));
+    return JMH_OK;
+}
+// jmh_convert_picture / jmh_convert_tensor: the host planes packed, uploaded to a scratch picture, the
+// same kernel, everything on the context's output stream and waited for
+static int convert_any(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const PullDst &d, void *stream) {
+    int r = check_pull_dst(c, d);
+    if (r) return r;
+    if (!y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    if ((r = output_stream(c))) return r;
+    std::vector<uint8_t> h(c->fsize);
+    if (!pack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
+    DevTemps tmp;
+    uint8_t *src = nullptr;
+    if (tmp.alloc(&src, c->fsize) != hipSuccess) return JMH_E_OOM;
+    if (stream) HCHK(hipStreamSynchronize((hipStream_t)stream));   // the destination's last consumer
+    hipError_t e = hipMemcpyAsync(src, h.data(), c->fsize, hipMemcpyHostToDevice, c->ost);
+    if (e == hipSuccess) r = pull_launch(c, d, src, c->ost);
+    const hipError_t se = hipStreamSynchronize(c->ost);   // before src and h are freed, whatever happened
+    HCHK(e);
+    if (r) return r;
+    HCHK(se);
+    return JMH_OK;
+}
+extern "C" {
+int jmh_pull_picture(jmh_ctx *c, int which, const jmh_device_picture_out *dst) {
+    if (!c || !dst) return JMH_E_INVALID_ARG;
+    return pull_any(c, which, PullDst{dst, nullptr}, dst->stream);
+}
+int jmh_pull_tensor(jmh_ctx *c, int which, const jmh_device_tensor_out *dst) {
+    if (!c || !dst) return JMH_E_INVALID_ARG;
+    return pull_any(c, which, PullDst{nullptr, dst}, dst->stream);
+}
+int jmh_convert_picture(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const jmh_device_picture_out *dst) {
+    if (!c || !dst) return JMH_E_INVALID_ARG;
+    return convert_any(c, y, u, v, sy, sc, PullDst{dst, nullptr}, dst->stream);
+}
+int jmh_convert_tensor(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const jmh_device_tensor_out *dst) {
+    if (!c || !dst) return JMH_E_INVALID_ARG;
+    return convert_any(c, y, u, v, sy, sc, PullDst{nullptr, dst}, dst->stream);
+}
+int jmh_device_output_wait(jmh_ctx *c) {
+    if (!c) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    return output_wait(c);
+}
+int jmh_device_download(jmh_ctx *c, void *dst, const void *src, size_t n, void *stream) {
+    if (!c || !dst || !src) return JMH_E_INVALID_ARG;
+    if (!n) return JMH_OK;
+    HCHK(hipSetDevice(c->dev));
+    hipStream_t st = (hipStream_t)stream;
+    if (!st) { int r = output_stream(c); if (r) return r; st = c->ost; }
+    HCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st));
+    HCHK(hipStreamSynchronize(st));
+    return JMH_OK;
+}
+// the inverse conversion of the flags (include/jmhip_output.h): needs no context
+int jmh_yuv_coefficients(int flags, int bit_depth, int32_t out[8]) {
+    if (!out || (flags & ~JMR_FLAGS) || (bit_depth != 8 && bit_depth != 10)) return JMH_E_INVALID_ARG;
+    jmout_coef k;
+    jmout_coefficients(flags, bit_depth, &k);
+    const int32_t w[8] = {k.iy, k.irv, k.igu, k.igv, k.ibu, k.yo, k.co, k.maxv};
+    memcpy(out, w, sizeof(w));
+    return JMH_OK;
+}
+// the dequantiser of a tensor's elements on the host: needs no context
+int jmh_tensor_dequantise(int dtype, int bit_depth, const int32_t *q, size_t n, void *elems) {
+    if (dtype < 0 || dtype >= JMT_NDTYPES || (n && (!elems || !q))) return JMH_E_INVALID_ARG;
+    if (!jmt_depth_ok(dtype, bit_depth)) return JMH_E_UNSUPPORTED_CFG;
+    const int32_t M = (1 << bit_depth) - 1;
+    uint8_t *p = (uint8_t *)elems;
+    for (size_t i = 0; i < n; i++) jmout_put(p + i * jmt_es(dtype), jmt_es(dtype), jmout_dequant(dtype, jmr_clip(q[i], M), M));
+    return JMH_OK;
+}
+}  // extern "C"
 
 // the conversion of an RGB format (include/jmhip_rgb.h): needs no context
 extern "C" int jmh_rgb_coefficients(int format, int bit_depth, int32_t out[12]) {

@@ -75,6 +75,10 @@ static const map_entry Map[] = {
     {"DeviceInputMatrix", 0, OFF(device_input_matrix), 0, 1},
     {"DeviceInputFullRange", 0, OFF(device_input_full), 0, 1},
     {"DeviceInputTensor", 0, OFF(device_input_tensor), 0, 4},
+    {"DeviceReconFormat", 0, OFF(device_recon_format), 0, 19},
+    {"DeviceReconTensor", 0, OFF(device_recon_tensor), 0, 4},
+    {"DeviceReconMatrix", 0, OFF(device_recon_matrix), 0, 1},
+    {"DeviceReconFullRange", 0, OFF(device_recon_full), 0, 1},
     {"DeviceNAL", 0, OFF(device_nal), 0, 1},
     {"JMVersion", 0, OFF(jm_version), 8, 99},
     {"QOffsetIntra", 0, OFF(qoff_intra), -1, JMH_QOFFSET_MAX},
@@ -197,6 +201,9 @@ jm_device_push_rgb_fn jm_device_input_rgb(void) { return device_input_rgb_fn; }
 static jm_device_push_tensor_fn device_input_tensor_fn;
 void jm_set_device_input_tensor(jm_device_push_tensor_fn fn) { device_input_tensor_fn = fn; }
 jm_device_push_tensor_fn jm_device_input_tensor(void) { return device_input_tensor_fn; }
+static jm_device_output_fn device_output_fn;
+void jm_set_device_output(jm_device_output_fn fn) { device_output_fn = fn; }
+jm_device_output_fn jm_device_output(void) { return device_output_fn; }
 
 int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->rdopt > 1) { snprintf(err, errlen, "RDOptimization=%d not supported (0 or 1)", inp->rdopt); return -1; }
@@ -227,6 +234,19 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->device_input_tensor == 4 && inp->bit_depth_luma != 8 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputTensor=4 (gbrpf32le) is quantised to 8 or 10 bits: it needs SourceBitDepthLuma=8 or 10 (got %d)", inp->bit_depth_luma); return -1; }
     if (inp->device_input_tensor && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV (InputFile=%s)", inp->device_input_tensor, inp->infile); return -1; }
     if (inp->device_input_tensor && !inp->device_writer_async) { snprintf(err, errlen, "DeviceInputTensor=%d leaves no YUV source on the host, so the distortion comes from the device's SSDs: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1)", inp->device_input_tensor); return -1; }
+    if (inp->device_recon_format && inp->device_recon_tensor) { snprintf(err, errlen, "DeviceReconFormat=%d and DeviceReconTensor=%d both name the layout of ReconFile: set one of them", inp->device_recon_format, inp->device_recon_tensor); return -1; }
+    if (inp->device_recon_format && inp->device_recon_format < 16) { snprintf(err, errlen, "DeviceReconFormat=%d not supported (0: YUV, 16 BGRA8, 17 RGBA8, 18 RGB10A2, 19 BGR10A2)", inp->device_recon_format); return -1; }
+    if ((inp->device_recon_matrix || inp->device_recon_full) && !inp->device_recon_format && !inp->device_recon_tensor) { snprintf(err, errlen, "DeviceReconMatrix / DeviceReconFullRange describe an RGB ReconFile: they need DeviceReconFormat=16..19 or DeviceReconTensor=1..4"); return -1; }
+    if (inp->device_recon_format || inp->device_recon_tensor) {
+        const char *key = inp->device_recon_format ? "DeviceReconFormat" : "DeviceReconTensor";
+        const int val = inp->device_recon_format ? inp->device_recon_format : inp->device_recon_tensor, bd = inp->bit_depth_luma;
+        if (!inp->reconfile[0]) { snprintf(err, errlen, "%s=%d names the layout of ReconFile: it needs ReconFile", key, val); return -1; }
+        if (!device_output_fn) { snprintf(err, errlen, "%s=%d converts the decoded picture on the device: it needs the device backend (this build has no device output: %s=0)", key, val, key); return -1; }
+        if (inp->device_recon_format && bd != (val >= 18 ? 10 : 8)) { snprintf(err, errlen, "DeviceReconFormat=%d holds %d-bit components: it needs SourceBitDepthLuma=%d (got %d)", val, val >= 18 ? 10 : 8, val >= 18 ? 10 : 8, bd); return -1; }
+        if (inp->device_recon_tensor && val < 3 && bd != 8) { snprintf(err, errlen, "DeviceReconTensor=%d holds 8-bit components: it needs SourceBitDepthLuma=8 (got %d)", val, bd); return -1; }
+        if (inp->device_recon_tensor == 3 && bd != 10) { snprintf(err, errlen, "DeviceReconTensor=3 (gbrp10le) holds 10-bit components: it needs SourceBitDepthLuma=10 (got %d)", bd); return -1; }
+        if (inp->device_recon_tensor == 4 && bd != 8 && bd != 10) { snprintf(err, errlen, "DeviceReconTensor=4 (gbrpf32le) is dequantised from 8 or 10 bits: it needs SourceBitDepthLuma=8 or 10 (got %d)", bd); return -1; }
+    }
     if (inp->symbol_mode && inp->profile_idc == 66) { snprintf(err, errlen, "SymbolMode=1 (CABAC) is not allowed in the Baseline profile (ProfileIDC=66)"); return -1; }
     if (inp->symbol_mode && inp->context_init_method) { snprintf(err, errlen, "ContextInitMethod=1 (adaptive CABAC model selection) not supported (0: FixedModelNumber)"); return -1; }
     if (inp->symbol_mode && inp->model_number) { snprintf(err, errlen, "FixedModelNumber=%d not supported (0: cabac_init_idc 0)", inp->model_number); return -1; }

@@ -396,6 +396,14 @@ static void job_release(wpool_t *P, int k) {
     pthread_mutex_unlock(&P->mu);
 }
 
+/* DeviceReconFormat / DeviceReconTensor: the current picture pulled on the device and appended to ReconFile */
+typedef struct { jm_device_output_fn fn; int format, tensor, flags, w, h; size_t bytes; uint8_t *buf; FILE *f; } drec_t;
+static int device_recon_write(const drec_t *d, const jm_backend *be) {
+    const int r = d->fn(be->ctx, d->format, d->tensor, d->flags, d->w, d->h, d->buf);
+    if (r) { fprintf(stderr, "device recon pull failed: %d\n", r); return r; }
+    return fwrite(d->buf, 1, d->bytes, d->f) == d->bytes ? 0 : JMH_E_INVALID_ARG;
+}
+
 int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *log) {
     memset(st, 0, sizeof(*st));
     if (inp->device_nal && !device_nal_fn) {
@@ -487,6 +495,28 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     /* pictures waiting for their results: depth > 1 when the backend pipelines (jmh_frame_push /
        jmh_frame_pop, lencod.c); their sources stay here for the PSNR */
     const int dev_dbk = be->read_deblocked && be->reference_deblocked;
+    /* DeviceReconFormat / DeviceReconTensor: ReconFile holds the picture converted on the device, pulled right
+       after its pop (while it is the current picture) and written then: pops come in picture order */
+    drec_t drec;
+    memset(&drec, 0, sizeof(drec));
+    if (inp->device_recon_format || inp->device_recon_tensor) {
+        drec.fn = jm_device_output();
+        drec.flags = (inp->device_recon_matrix ? JMH_PIX_BT709 : 0) | (inp->device_recon_full ? JMH_PIX_FULL_RANGE : 0);
+        drec.format = inp->device_recon_format ? inp->device_recon_format | drec.flags : 0;
+        drec.tensor = inp->device_recon_tensor;
+        drec.w = inp->width; drec.h = inp->height;
+        drec.bytes = jm_recon_frame_bytes(drec.tensor, drec.w, drec.h);
+        drec.f = frec;
+        if (!drec.fn || !frec || !dev_dbk || !(drec.buf = (uint8_t *)malloc(drec.bytes))) {
+            fprintf(stderr, "DeviceRecon%s=%d needs ReconFile and the device backend with device deblocking (backend '%s')\n",
+                    drec.tensor ? "Tensor" : "Format", drec.tensor ? drec.tensor : inp->device_recon_format, be->name);
+            if (fin) fclose(fin);
+            fclose(fout);
+            if (frec) fclose(frec);
+            free(drec.buf);
+            return JMH_E_UNSUPPORTED_CFG;
+        }
+    }
     const int pipelined = dev_dbk && be->push && be->pop && be->depth > 1;
     const int depth = pipelined ? be->depth : 1;
     const int async = inp->device_writer_async;
@@ -496,6 +526,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         if (fin) fclose(fin);
         fclose(fout);
         if (frec) fclose(frec);
+        free(drec.buf);
         return JMH_E_UNSUPPORTED_CFG;
     }
     /* parallel slice writing: pipelined device backend, not with the call surface's per-MB
@@ -522,6 +553,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         if (fin) fclose(fin);
         fclose(fout);
         if (frec) fclose(frec);
+        free(drec.buf);
         return JMH_E_OOM;
     }
     if (device_input_fn) {   /* the readers write the display size only: what lies outside is the device's to pad, never this */
@@ -592,6 +624,12 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             fprintf(log, " (the source is an RGB tensor, %s: quantised and converted on the device with the BT.%s matrix at %s range; the stream does not signal either)\n",
                     tensor_kind == 1 ? "rgb24" : tensor_kind == 2 ? "gbrp" : tensor_kind == 3 ? "gbrp10le" : "gbrpf32le",
                     inp->device_input_matrix ? "709" : "601", inp->device_input_full ? "full" : "limited");
+        if (drec.fn)
+            fprintf(log, " (ReconFile holds %s %s: the display-size picture converted on the device with the BT.%s matrix at %s range and downloaded)\n",
+                    drec.tensor ? "an RGB tensor," : "RGB, format",
+                    drec.tensor == 1 ? "rgb24" : drec.tensor == 2 ? "gbrp" : drec.tensor == 3 ? "gbrp10le" : drec.tensor == 4 ? "gbrpf32le"
+                    : inp->device_recon_format == 16 ? "16" : inp->device_recon_format == 17 ? "17" : inp->device_recon_format == 18 ? "18" : "19",
+                    inp->device_recon_matrix ? "709" : "601", inp->device_recon_full ? "full" : "limited");
         if (device_input_fn) fprintf(log, " (the source is uploaded as read and pushed from device memory: the device pads it to the coded size)\n");
         if (async) fprintf(log, " (the slice writer is queued behind each picture: its pop returns the slice bytes and the SSDs)\n");
         if (nal) fprintf(log, " (NAL units finished on the device: the pop returns the picture's access unit)\n");
@@ -609,7 +647,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         pool_wait(&pool, (int)(fj_ - pool.jobs));                                                   \
         if (fj_->status) { st_ret = fj_->status; break; }                                           \
         fwrite(fj_->out.buf, 1, fj_->out.len, fout);                                                 \
-        if (frec) jm_write_yuv_frame(frec, &fj_->rec, inp->width, inp->height);                     \
+        if (frec && !drec.fn) jm_write_yuv_frame(frec, &fj_->rec, inp->width, inp->height);         \
         st->psnr_y += fj_->py; st->psnr_u += fj_->pu; st->psnr_v += fj_->pv;                          \
         st->bits += fj_->pic_bits;                                                                  \
         im.rate_checked += fj_->im.rate_checked; im.rate_mismatches += fj_->im.rate_mismatches;     \
@@ -637,6 +675,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         memcpy(j_->im.mb_data, r0_, (size_t)nmb * sizeof(jmh_mb_result));                         \
         int r_ = be->read_deblocked(be->ctx, &j_->rec);                                            \
         if (r_) { fprintf(stderr, "read_deblocked failed: %d\n", r_); st_ret = r_; break; }       \
+        if (drec.fn && (r_ = device_recon_write(&drec, be))) { st_ret = r_; break; }               \
         copy_ms += now_ms() - t1;                                                                  \
         st->deblock_ms += now_ms() - t1;                                                           \
         j_->cur = &p_->cur; j_->fp = p_->fp; j_->f = p_->f; j_->is_i = p_->is_i; j_->met = (MET_MS); \
@@ -673,7 +712,8 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         double t3 = now_ms();                                                                      \
         st->deblock_ms += t3 - t2;                                                                 \
         if (r_) { fprintf(stderr, "set_reference failed: %d\n", r_); st_ret = r_; break; }         \
-        if (frec) jm_write_yuv_frame(frec, &rec, inp->width, inp->height);                         \
+        if (drec.fn) { if ((r_ = device_recon_write(&drec, be))) { st_ret = r_; break; } }         \
+        else if (frec) jm_write_yuv_frame(frec, &rec, inp->width, inp->height);                    \
         double py = psnr_pl(&p_->cur, &rec, 0, inp->width, inp->height);                           \
         double pu = psnr_pl(&p_->cur, &rec, 1, inp->width / 2, inp->height / 2);                   \
         double pv = psnr_pl(&p_->cur, &rec, 2, inp->width / 2, inp->height / 2);                   \
@@ -706,7 +746,8 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         long pic_bits = out.len * 8;                                                               \
         fwrite(out.buf, 1, out.len, fout);                                                         \
         out.len = 0;                                                                               \
-        if (frec) {                                                                                \
+        if (drec.fn) { int r_ = device_recon_write(&drec, be); if (r_) { st_ret = r_; break; } }   \
+        else if (frec) {                                                                           \
             int r_ = be->read_deblocked(be->ctx, &rec);                                            \
             if (r_) { fprintf(stderr, "read_deblocked failed: %d\n", r_); st_ret = r_; break; }    \
             jm_write_yuv_frame(frec, &rec, inp->width, inp->height);                               \
@@ -867,5 +908,6 @@ cleanup:
     if (fin) fclose(fin);
     fclose(fout);
     if (frec) fclose(frec);
+    free(drec.buf);
     return st_ret;
 }

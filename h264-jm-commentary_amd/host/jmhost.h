@@ -100,6 +100,15 @@ typedef struct jm_input {
                                   planes; 8- or 10-bit).  A frame is uploaded raw and pushed as a device tensor
                                   (include/jmhip_tensor.h); DeviceInputMatrix / DeviceInputFullRange apply.  0: off.
                                   Needs DeviceWriterAsync 1; excludes DeviceInputFormat                      */
+    int  device_recon_format;  /* (this build) DeviceReconFormat 16..19: ReconFile holds the display-size picture
+                                  converted on the device to packed RGB (height rows of 4 * width bytes, the
+                                  layouts of DeviceInputFormat; jmh_pull_picture of include/jmhip_output.h) and
+                                  fetched with jmh_device_download, where it otherwise holds YUV.  0: YUV      */
+    int  device_recon_tensor;  /* (this build) DeviceReconTensor 1..4: the same as an RGB tensor, in the file
+                                  layouts of DeviceInputTensor (rgb24, gbrp, gbrp10le, gbrpf32le; jmh_pull_tensor).
+                                  Excludes DeviceReconFormat.  0: off                                           */
+    int  device_recon_matrix;  /* (this build) DeviceReconMatrix 1: BT.709 (0: BT.601); the stream signals neither (no VUI) */
+    int  device_recon_full;    /* (this build) DeviceReconFullRange 1: full range (0: limited)                    */
     int  device_nal;           /* (this build) DeviceNAL 1: with DeviceWriterAsync 1 the NAL units are finished
                                   on the device behind the slice writer (jmh_coded_nal_heads): the pop
                                   returns the picture's Annex B access unit, appended to the stream in
@@ -297,9 +306,18 @@ typedef int (*jm_device_push_tensor_fn)(void *ctx, const void *frame, int kind, 
                                         int n, const jmh_coded_slice *slices, int crop_w, int crop_h);
 void jm_set_device_input_tensor(jm_device_push_tensor_fn fn);
 jm_device_push_tensor_fn jm_device_input_tensor(void);
+/* DeviceReconFormat 16..19 / DeviceReconTensor 1..4: the backend's pull of the current picture, deblocked, at the
+   display size into dst on the host (jmh_pull_picture / jmh_pull_tensor, then jmh_device_download): format with
+   its flags and tensor 0, or format 0, tensor 1..4 and flags.  dst holds jm_recon_frame_bytes bytes.  Registered
+   before jm_configure: PatchInp rejects the keys on a backend without one */
+typedef int (*jm_device_output_fn)(void *ctx, int format, int tensor, int flags, int disp_w, int disp_h, void *dst);
+void jm_set_device_output(jm_device_output_fn fn);
+jm_device_output_fn jm_device_output(void);
 /* bytes of an element and of a frame of a DeviceInputTensor file */
 static inline int jm_tensor_elem_bytes(int kind) { return kind == 4 ? 4 : kind == 3 ? 2 : 1; }
 static inline size_t jm_tensor_frame_bytes(int kind, int w, int h) { return (size_t)3 * jm_tensor_elem_bytes(kind) * w * h; }
+/* bytes of a frame of a ReconFile written with DeviceReconFormat (tensor 0) or DeviceReconTensor */
+static inline size_t jm_recon_frame_bytes(int tensor, int w, int h) { return tensor ? jm_tensor_frame_bytes(tensor, w, h) : (size_t)4 * w * h; }
 /* 10 log10(peak^2 w h / ssd) with psnr_pl's arithmetic (99.0 at ssd 0): the PSNR of a w x h plane of
    bit_depth-bit samples from its summed squared error */
 double jm_psnr_from_ssd(uint64_t ssd, int w, int h, int bit_depth);

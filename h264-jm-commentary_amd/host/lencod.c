@@ -131,10 +131,53 @@ static int gpu_push_device_tensor(void *ctx, const void *frame, int kind, int fl
     t.stream = gpu_in.stream;
     return jmh_frame_push_coded_tensor((jmh_ctx *)ctx, &t, fp, n, sl, cw, ch);
 }
+/* DeviceReconFormat 16..19 / DeviceReconTensor 1..4: the current picture, deblocked, pulled at the display size into
+   one device buffer in the file's layout, on a stream of the caller's, and downloaded behind it */
+static struct { void *buf, *stream; size_t bytes; } gpu_out;
+static int gpu_pull_recon(void *ctx, int format, int tensor, int flags, int dw, int dh, void *dst) {
+    const size_t bytes = jm_recon_frame_bytes(tensor, dw, dh);
+    int r;
+    if (!gpu_out.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_out.stream))) return r;
+    if (gpu_out.bytes < bytes) {
+        if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_out.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_out.buf))) return r;
+        gpu_out.bytes = bytes;
+    }
+    uint8_t *base = (uint8_t *)gpu_out.buf;
+    if (!tensor) {
+        jmh_device_picture_out pic;
+        memset(&pic, 0, sizeof(pic));
+        pic.format = format;
+        pic.width = dw; pic.height = dh;
+        pic.plane[0] = base;
+        pic.stride[0] = (int64_t)4 * dw;
+        pic.stream = gpu_out.stream;
+        r = jmh_pull_picture((jmh_ctx *)ctx, JMH_OUT_DEBLOCKED, &pic);
+    } else {
+        const size_t es = (size_t)jm_tensor_elem_bytes(tensor), plane = es * dw * dh;
+        jmh_device_tensor_out t;
+        memset(&t, 0, sizeof(t));
+        t.dtype = tensor == 4 ? JMH_T_F32 : tensor == 3 ? JMH_T_U16 : JMH_T_U8;
+        t.flags = flags;
+        t.width = dw; t.height = dh;
+        if (tensor == 1) {   /* rgb24: pixels of R, G, B */
+            t.chan[0] = base; t.chan[1] = base + 1; t.chan[2] = base + 2;
+            t.stride_x = 3; t.stride_y = (int64_t)3 * dw;
+        } else {             /* gbrp*: planes G, B, R */
+            t.chan[0] = base + 2 * plane; t.chan[1] = base; t.chan[2] = base + plane;
+            t.stride_x = (int64_t)es; t.stride_y = (int64_t)es * dw;
+        }
+        t.stream = gpu_out.stream;
+        r = jmh_pull_tensor((jmh_ctx *)ctx, JMH_OUT_DEBLOCKED, &t);
+    }
+    return r ? r : jmh_device_download((jmh_ctx *)ctx, dst, gpu_out.buf, bytes, gpu_out.stream);
+}
 static void gpu_input_release(void *ctx) {
     if (gpu_in.stream) (void)jmh_device_stream_destroy((jmh_ctx *)ctx, gpu_in.stream);
     if (gpu_in.buf) (void)jmh_device_free((jmh_ctx *)ctx, gpu_in.buf);
     memset(&gpu_in, 0, sizeof(gpu_in));
+    if (gpu_out.stream) (void)jmh_device_stream_destroy((jmh_ctx *)ctx, gpu_out.stream);
+    if (gpu_out.buf) (void)jmh_device_free((jmh_ctx *)ctx, gpu_out.buf);
+    memset(&gpu_out, 0, sizeof(gpu_out));
 }
 
 int main(int argc, char **argv) {
@@ -144,6 +187,7 @@ int main(int argc, char **argv) {
     jm_set_device_input(gpu_push_device);   /* before PatchInp: it rejects DeviceInput on a backend without one */
     jm_set_device_input_rgb(gpu_push_device_rgb);
     jm_set_device_input_tensor(gpu_push_device_tensor);
+    jm_set_device_output(gpu_pull_recon);
     if (jm_configure(&inp, argc, argv, err, sizeof(err))) { fprintf(stderr, "%s\n", err); return 1; }
     jmh_config cfg;
     jm_fill_config(&inp, &cfg);

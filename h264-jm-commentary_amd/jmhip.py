@@ -312,6 +312,30 @@ _SIGS_TENSOR = {
 }
 EXPORTED_TENSOR = list(_SIGS_TENSOR)
 
+# ---- decoded pictures pulled on the device (include/jmhip_output.h; additive to ABI 14) ----
+JMH_OUT_DEBLOCKED, JMH_OUT_RECON = 0, 1
+
+
+class JmhDevicePictureOut(ctypes.Structure):
+    _fields_ = JmhDevicePicture._fields_
+
+
+class JmhDeviceTensorOut(ctypes.Structure):
+    _fields_ = JmhDeviceTensor._fields_
+
+
+_SIGS_OUTPUT = {
+    "jmh_pull_picture": (_I, [_P, _I, _P]),
+    "jmh_pull_tensor": (_I, [_P, _I, _P]),
+    "jmh_convert_picture": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "jmh_convert_tensor": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "jmh_device_output_wait": (_I, [_P]),
+    "jmh_device_download": (_I, [_P, _P, _P, ctypes.c_size_t, _P]),
+    "jmh_yuv_coefficients": (_I, [_I, _I, _P]),
+    "jmh_tensor_dequantise": (_I, [_I, _I, _P, ctypes.c_size_t, _P]),
+}
+EXPORTED_OUTPUT = tuple(_SIGS_OUTPUT)
+
 # ---- the unit seam of the searches' spiral decode (include/jmhip_spiral.h; additive to ABI 14);
 #      bound where it is called (Encoder.spiral_positions), so that a library built before it loads
 _SIGS_SPIRAL = {
@@ -538,6 +562,149 @@ def to_device_tensor(array, layout="chw", order="rgb", flags=0, pad_stride=0, mi
     return TensorLayout(dt, flags, w, h, buf[:end].copy(), [misalign + c * es for c in where], C * es, stride_y)
 
 
+def yuv_coefficients(flags, bit_depth):
+    """jmh_yuv_coefficients: the inverse conversion of the flags (JMH_PIX_BT709 | JMH_PIX_FULL_RANGE) at
+    a bit depth of 8 or 10, as 8 ints: iy, irv, igu, igv, ibu, then Yo, Co and M.  Needs no device."""
+    out = (ctypes.c_int32 * 8)()
+    _check(load().jmh_yuv_coefficients(flags, bit_depth, out), "jmh_yuv_coefficients")
+    return [int(v) for v in out]
+
+
+_TENSOR_STORAGE = {JMH_T_U8: np.uint8, JMH_T_U16: np.uint16, JMH_T_F16: np.float16, JMH_T_BF16: np.uint16, JMH_T_F32: np.float32}
+
+
+def tensor_dequantise(q, dtype, bit_depth):
+    """jmh_tensor_dequantise: the elements that hold the integer components q (any shape, clamped to
+    [0, 2^bit_depth - 1]) as a numpy array of the same shape: uint8, uint16, float16 or float32;
+    bfloat16 comes as its uint16 bits.  Needs no device."""
+    q = np.ascontiguousarray(q, np.int32)
+    out = np.empty(q.shape, _TENSOR_STORAGE[dtype])
+    _check(load().jmh_tensor_dequantise(dtype, bit_depth, _ptr(q), q.size, _ptr(out)), "jmh_tensor_dequantise")
+    return out
+
+
+class DevicePictureOut(DevicePicture):
+    """jmh_device_picture_out: a DevicePicture whose planes the library writes (Encoder.pull / convert);
+    stream: the stream the pull is queued on, or None for a picture that is complete on return."""
+
+    def struct(self):
+        s = JmhDevicePictureOut()
+        ctypes.memmove(ctypes.byref(s), ctypes.byref(DevicePicture.struct(self)), ctypes.sizeof(s))
+        return s
+
+
+class DeviceTensorOut(DeviceTensor):
+    """jmh_device_tensor_out: a DeviceTensor whose channels the library writes (Encoder.pull_tensor /
+    convert_tensor)."""
+
+    def struct(self):
+        s = JmhDeviceTensorOut()
+        ctypes.memmove(ctypes.byref(s), ctypes.byref(DeviceTensor.struct(self)), ctypes.sizeof(s))
+        return s
+
+
+def _rows_view(buf, offset, rows, row_bytes, stride):
+    return np.lib.stride_tricks.as_strided(buf[offset:], (rows, row_bytes), (stride, 1))
+
+
+class OutLayout:
+    """What out_layout lays out: a destination of nbytes bytes, the planes' byte offsets in it and
+    their strides.  at(base) is its DevicePictureOut at a device address; planes(buf) reads the
+    picture out of the block's bytes; mask() marks the bytes that are destination elements."""
+
+    def __init__(self, format, width, height, nbytes, offsets, strides, shapes, itemsize):
+        self.format, self.width, self.height, self.nbytes = format, width, height, nbytes
+        self.offsets, self.strides, self.shapes, self.itemsize = offsets, strides, shapes, itemsize
+
+    def at(self, base, stream=None):
+        return DevicePictureOut(self.format, self.width, self.height, [_addr(base) + o for o in self.offsets], self.strides, stream)
+
+    def planes(self, buf):
+        """the planes as arrays: (y, u, v), (y, uv) of NV12 / P010, or one (h, w) uint32 array of RGB"""
+        buf = np.ascontiguousarray(buf, np.uint8)
+        dt = {1: np.uint8, 2: np.uint16, 4: np.uint32}[self.itemsize]
+        return [_rows_view(buf, o, r, n * self.itemsize, st).copy().view(dt) for o, st, (r, n) in zip(self.offsets, self.strides, self.shapes)]
+
+    def mask(self):
+        m = np.zeros(self.nbytes, bool)
+        for o, st, (r, n) in zip(self.offsets, self.strides, self.shapes):
+            _rows_view(m, o, r, n * self.itemsize, st)[:] = True
+        return m
+
+
+def out_layout(format, width, height, pad_stride=0, misalign=0, guard=0):
+    """A destination for Encoder.pull / convert in a format of jmhip_input.h or jmhip_rgb.h (with its
+    flags), as an OutLayout.  pad_stride: bytes added to every row; misalign: the offset in bytes
+    of every plane's first element from a 256-byte boundary of the block; guard: bytes of the block
+    in front of the first plane (rounded up to that boundary) and behind the last element."""
+    lay = format & ~(JMH_PIX_BT709 | JMH_PIX_FULL_RANGE)
+    if lay >= JMH_PIX_BGRA8:
+        es, shapes = 4, [(height, width)]
+    else:
+        es = 2 if lay >= JMH_PIX_I010 else 1
+        shapes = [(height, width), (height // 2, width)] if lay in (JMH_PIX_NV12, JMH_PIX_P010) else \
+            [(height, width), (height // 2, width // 2), (height // 2, width // 2)]
+    offsets, strides, end = [], [], guard
+    for r, n in shapes:
+        offsets.append((end + 255) // 256 * 256 + misalign)
+        strides.append(n * es + pad_stride)
+        end = offsets[-1] + (r - 1) * strides[-1] + n * es
+    return OutLayout(format, width, height, end + guard, offsets, strides, shapes, es)
+
+
+class OutTensorLayout:
+    """What out_tensor_layout lays out: a destination of nbytes bytes, the byte offsets of R, G and B
+    at pixel (0, 0) in it and the two strides.  at(base) is its DeviceTensorOut; channels(buf) reads
+    R, G, B (h x w each, bfloat16 as uint16 bits) out of the block's bytes; mask() marks the bytes that
+    are destination elements."""
+
+    def __init__(self, dtype, flags, width, height, nbytes, offsets, stride_x, stride_y):
+        self.dtype, self.flags, self.width, self.height, self.nbytes = dtype, flags, width, height, nbytes
+        self.offsets, self.stride_x, self.stride_y = offsets, stride_x, stride_y
+
+    def at(self, base, stream=None):
+        return DeviceTensorOut(self.dtype, self.flags, self.width, self.height, [_addr(base) + o for o in self.offsets], self.stride_x,
+                               self.stride_y, stream)
+
+    def _view(self, buf, offset):
+        es = TENSOR_ELEM_BYTES[self.dtype]
+        return np.lib.stride_tricks.as_strided(buf[offset:], (self.height, self.width, es), (self.stride_y, self.stride_x, 1))
+
+    def channels(self, buf):
+        buf = np.ascontiguousarray(buf, np.uint8)
+        return [np.ascontiguousarray(self._view(buf, o)).view(_TENSOR_STORAGE[self.dtype]).reshape(self.height, self.width) for o in self.offsets]
+
+    def mask(self):
+        m = np.zeros(self.nbytes, bool)
+        for o in self.offsets:
+            self._view(m, o)[:] = True
+        return m
+
+
+def out_tensor_layout(dtype, width, height, layout="chw", order="rgb", channels=3, flags=0, pad_stride=0, misalign=0, guard=0):
+    """A destination for Encoder.pull_tensor / convert_tensor, as an OutTensorLayout: layout "chw"
+    (three planes) or "hwc" with channels 3 or 4 (the fourth is never written); order: which channel
+    of the array holds which component ("rgb", "bgr", ...).  pad_stride, misalign (multiples of the
+    element size) and guard as for out_layout."""
+    es = TENSOR_ELEM_BYTES[dtype]
+    if layout not in ("chw", "hwc") or sorted(order) != ["b", "g", "r"] or channels not in (3, 4) or (layout == "chw" and channels != 3):
+        raise ValueError("out_tensor_layout takes layout 'chw' or 'hwc', 3 (or for 'hwc' 4) channels and an order that is a permutation of 'rgb'")
+    if misalign % es or pad_stride % es:
+        raise ValueError("misalign and pad_stride are multiples of the element size")
+    where = [order.index(c) for c in "rgb"]
+    if layout == "chw":
+        stride_y = width * es + pad_stride
+        starts, end = [], guard
+        for _ in range(3):
+            starts.append((end + 255) // 256 * 256 + misalign)
+            end = starts[-1] + (height - 1) * stride_y + width * es
+        return OutTensorLayout(dtype, flags, width, height, end + guard, [starts[c] for c in where], es, stride_y)
+    stride_y = width * channels * es + pad_stride
+    start = (guard + 255) // 256 * 256 + misalign
+    end = start + (height - 1) * stride_y + ((width - 1) * channels + 3) * es      # the last pixel's three channels
+    return OutTensorLayout(dtype, flags, width, height, end + guard, [start + c * es for c in where], channels * es, stride_y)
+
+
 def pad_to_coded(pics, cw, ch):
     """host/yuv.c jm_pad_picture in numpy: (y, u, v) of the source size replicated to cw x ch."""
     out = []
@@ -592,7 +759,8 @@ def load(path=LIB_PATH):
         raise JmhError(f"libjmhip.so not found at {path}: build it with __graft_entry__.build()")
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()) + \
-            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()) + list(_SIGS_NAL.items()) + list(_SIGS_RGB.items()) + list(_SIGS_TENSOR.items()):
+            list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()) + list(_SIGS_NAL.items()) + list(_SIGS_RGB.items()) + list(_SIGS_TENSOR.items()) + \
+            list(_SIGS_OUTPUT.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -956,6 +1124,71 @@ class Encoder:
         s = t.struct()
         _check(self.lib.jmh_ingest_tensor(self.ctx, ctypes.byref(s), _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2), "jmh_ingest_tensor")
         return y, u, v
+
+    # ---- decoded pictures pulled on the device (include/jmhip_output.h) ----
+    def pull(self, dst, which=JMH_OUT_DEBLOCKED):
+        """jmh_pull_picture: the current picture (the one the last pop returned), deblocked or
+        JMH_OUT_RECON, cropped to dst's size and written into the planes of a DevicePictureOut, queued
+        on dst.stream (None: complete on return)."""
+        s = dst.struct()
+        _check(self.lib.jmh_pull_picture(self.ctx, which, ctypes.byref(s)), "jmh_pull_picture")
+
+    def pull_tensor(self, dst, which=JMH_OUT_DEBLOCKED):
+        """jmh_pull_tensor: the same, converted to RGB and dequantised into a DeviceTensorOut."""
+        s = dst.struct()
+        _check(self.lib.jmh_pull_tensor(self.ctx, which, ctypes.byref(s)), "jmh_pull_tensor")
+
+    def convert(self, y, u, v, dst):
+        """jmh_convert_picture, the unit seam: host planes of the coded size through the pull's kernel
+        into a DevicePictureOut; complete on return."""
+        y, u, v = self._planes(y, u, v)
+        s = dst.struct()
+        _check(self.lib.jmh_convert_picture(self.ctx, _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2, ctypes.byref(s)), "jmh_convert_picture")
+
+    def convert_tensor(self, y, u, v, dst):
+        """jmh_convert_tensor, the unit seam: the same into a DeviceTensorOut."""
+        y, u, v = self._planes(y, u, v)
+        s = dst.struct()
+        _check(self.lib.jmh_convert_tensor(self.ctx, _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2, ctypes.byref(s)), "jmh_convert_tensor")
+
+    def device_out(self, layout, stream=None):
+        """An OutLayout / OutTensorLayout (out_layout, out_tensor_layout) allocated: a new allocation of
+        exactly its bytes (the caller frees .base).  Returns the DevicePictureOut / DeviceTensorOut."""
+        base = self.device_alloc(layout.nbytes)
+        d = layout.at(base, stream)
+        d.base = base
+        return d
+
+    def output_wait(self):
+        """jmh_device_output_wait: every pull queued so far has completed."""
+        _check(self.lib.jmh_device_output_wait(self.ctx), "jmh_device_output_wait")
+
+    def device_download(self, addr, nbytes, stream=None):
+        """jmh_device_download: nbytes of device memory at addr as a uint8 array, copied behind the
+        work queued on stream so far."""
+        out = np.empty(nbytes, np.uint8)
+        _check(self.lib.jmh_device_download(self.ctx, _ptr(out), _addr(addr), nbytes, stream), "jmh_device_download")
+        return out
+
+    def into_torch(self, t, order="rgb", flags=0, which=JMH_OUT_DEBLOCKED, layout=None):
+        """The current picture pulled into a torch tensor on this context's device, with no copy: any
+        (3, h, w) or (h, w, 3 or 4) tensor or view that from_torch would take, h x w being the crop.
+        The pull is queued on the stream torch is currently queueing on for t's device, so torch work
+        issued afterwards on that stream sees the picture; where that is the null stream, which cannot
+        be ordered against, it is synchronised and the picture is complete on return."""
+        d = self.from_torch(t, layout, order, flags)
+        self.pull_tensor(DeviceTensorOut(d.dtype, d.flags, d.width, d.height, d.chans, d.stride_x, d.stride_y, d.stream), which)
+        return t
+
+    def to_torch(self, dtype, layout="chw", flags=0, size=None, which=JMH_OUT_DEBLOCKED, device=None):
+        """into_torch of a new tensor: dtype a torch dtype (uint8, uint16, float16, bfloat16, float32),
+        layout "chw" for (3, h, w) or "hwc" for (h, w, 3), size (width, height) of the crop, default the
+        coded size."""
+        import torch                                           # not at module load
+        w, h = size if size is not None else (self.w, self.h)
+        dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        t = torch.empty((3, h, w) if layout == "chw" else (h, w, 3), dtype=dtype, device=dev)
+        return self.into_torch(t, flags=flags, which=which, layout=layout)
 
     def input_wait(self):
         """jmh_device_input_wait: the last pushed device picture has been read; its planes are free."""
