@@ -310,6 +310,19 @@ struct OutArgs {
     jmout_coef k;                        // the conversion of the flags at the context's bit depth (a YUV format: maxv only)
 };
 
+// k_scale (jmh_scale.hip): the top-left w x h of a packed sW x sH picture resampled to ow x oh and padded into the
+// packed W x H source.  The tables of jmh_scale.h (jms_pack_axis), [0] luma, [1] chroma (U and V share them)
+struct ScaleArgs {
+    const uint8_t *src;                  // Y, U, V of sW x sH, samples of 1 or 2 bytes (maxv > 255: 2)
+    uint8_t *dst;                        // Y, U, V of the coded size
+    int w, h, sW, sH, ow, oh, W, H;
+    const int32_t *fh[2], *fv[2];        // first of every output column / row
+    const uint32_t *th[2], *tv[2];       // JMS_HPAIRS dwords per column, JMS_VPAIRS per row
+    int nph[2], npv[2];                  // the pairs in use: T / 2 horizontally, T / 2 + 1 vertically
+    int tv_taps[2];                      // T of the vertical axis
+    int maxv, P;                         // (1 << bit depth) - 1, 14 - bit depth
+};
+
 // The stores of the converting ingest kernels (k_ingest_rgb, k_ingest_tensor): 8 luma samples of a row or 4 + 4
 // chroma samples, packed little-endian; TEN: 16-bit samples
 template <bool TEN>

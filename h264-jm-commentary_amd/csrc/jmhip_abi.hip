@@ -24,6 +24,7 @@
 #include "jmh_cabac.h"
 #include "jmh_cabac_rate.h"
 #include "jmh_ingest.h"
+#include "jmh_scale.h"
 #include "jmh_rgb.h"
 #include "jmh_tensor.h"
 #include "jmh_output.h"
@@ -179,6 +180,21 @@ struct Flight {
 
 enum { REF_NONE, REF_BUF, REF_REC, REF_DBK };
 
+static_assert(JMS_INVALID == JMH_E_INVALID_ARG && JMS_UNSUPPORTED == JMH_E_UNSUPPORTED_CFG && JMS_TAPS_MAX == JMH_SCALE_TAPS_MAX &&
+              JMS_SRC_MAX == JMH_SCALE_SRC_MAX && JMS_LANCZOS3 == JMH_SCALE_LANCZOS3 && JMS_CHROMA_LEFT == JMH_SCALE_CHROMA_LEFT, "jmh_scale.h restates jmhip_scale.h");
+// the tables of one geometry of the scaler (jmh_scale.h, jms_pack_axis) on the device; h: what was uploaded, kept
+// while the copy may be pending (up)
+#define SCALE_TABS 8
+struct ScaleTab {
+    int key[6];                          // source w, h, output w, h, filter, flags
+    uint8_t *d = nullptr;
+    std::vector<uint8_t> h;
+    hipEvent_t up = nullptr;
+    size_t off[2][4];                    // [luma, chroma][fh, fv, th, tv]: bytes into d
+    int T[2][2];                         // [luma, chroma][horizontal, vertical]
+    uint64_t used = 0;
+};
+
 struct jmh_ctx {
     jmh_config cfg;
     int dev;
@@ -268,6 +284,13 @@ struct jmh_ctx {
     size_t up_cap = 0;
     hipEvent_t ev_up = nullptr;          //   the last copy out of it
     hipStream_t ost = nullptr;           // pulls without a caller's stream, the convert seams, downloads (created on first use)
+    // jmh_input_scale (jmhip_scale.h): the setting (filter 0: off), the tables of the geometries last used and the
+    // scratch picture the ingest kernels pack into.  All of it is allocated, written, read and released on st
+    jmh_scale scale = {0, 0, 0, 0};
+    std::vector<ScaleTab> scale_tabs;
+    uint64_t scale_tick = 0;
+    uint8_t *d_scl = nullptr;
+    size_t scl_cap = 0;
 };
 
 #define HCHK(x)                                                                  \
@@ -446,6 +469,11 @@ void jmh_destroy(jmh_ctx *c) {
     if (c->nalw.out) (void)hipFree(c->nalw.out);
     if (c->nalw.h) (void)hipHostFree(c->nalw.h);
     if (c->nalw_pay) (void)hipFree(c->nalw_pay);
+    for (ScaleTab &t : c->scale_tabs) {
+        if (t.d) (void)hipFree(t.d);
+        if (t.up) (void)hipEventDestroy(t.up);
+    }
+    if (c->d_scl) (void)hipFree(c->d_scl);
     if (c->d_clamp) (void)hipFree(c->d_clamp);
     if (c->h_clamp) (void)hipHostFree(c->h_clamp);
     if (c->up_h) (void)hipHostFree(c->up_h);
@@ -1242,16 +1270,105 @@ struct PushSrc { const void *y, *u, *v; int sy, sc; bool wide; const jmh_device_
 // the argument rules of jmhip_input.h (formats 0..3, no flag) and of jmhip_rgb.h (16..19 with their flags)
 static int check_device_pic(const jmh_ctx *c, const jmh_device_picture *p) {
     if (!p) return JMH_E_INVALID_ARG;
-    if (jmr_is_rgb(p->format) ? jmr_check(p->format, p->width, p->height, c->W, c->H, p->plane, p->stride)
-                              : jmi_check(p->format, p->width, p->height, c->W, c->H, p->plane, p->stride)) return JMH_E_INVALID_ARG;
-    return JMH_OK;
+    const bool sc = c->scale.filter != JMH_SCALE_OFF;   // the source bound is the scaler's, not the coded size
+    const int BW = sc ? JMS_SRC_MAX : c->W, BH = sc ? JMS_SRC_MAX : c->H;
+    if (jmr_is_rgb(p->format) ? jmr_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)
+                              : jmi_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)) return JMH_E_INVALID_ARG;
+    return sc ? jms_check(p->width, p->height, c->scale.out_width, c->scale.out_height, c->scale.filter) : JMH_OK;
 }
 // whether a context of this bit depth takes the (checked) format
 static bool device_depth_ok(const jmh_ctx *c, int format) { return jmr_is_rgb(format) ? jmr_depth_ok(format, c->bd) : jmi_depth_ok(format, c->bd); }
 
 // the argument rules of jmhip_tensor.h
 static int check_device_tensor(const jmh_ctx *c, const jmh_device_tensor *t) {
-    if (!t || jmt_check(t->dtype, t->flags, t->width, t->height, c->W, c->H, t->chan, t->stride_x, t->stride_y)) return JMH_E_INVALID_ARG;
+    const bool sc = c->scale.filter != JMH_SCALE_OFF;
+    const int BW = sc ? JMS_SRC_MAX : c->W, BH = sc ? JMS_SRC_MAX : c->H;
+    if (!t || jmt_check(t->dtype, t->flags, t->width, t->height, BW, BH, t->chan, t->stride_x, t->stride_y)) return JMH_E_INVALID_ARG;
+    return sc ? jms_check(t->width, t->height, c->scale.out_width, c->scale.out_height, c->scale.filter) : JMH_OK;
+}
+
+// The tables of a w x h source under the current setting: the cached ones, or built and uploaded on st.  The entry
+// given up for them is the one used longest ago: its device memory is released in stream order behind its last
+// reader, its host copy after the upload out of it
+static int scale_tables(jmh_ctx *c, int w, int h, ScaleTab **out) {
+    const jmh_scale &s = c->scale;
+    const int key[6] = {w, h, s.out_width, s.out_height, s.filter, s.flags};
+    c->scale_tick++;
+    ScaleTab *slot = nullptr;
+    for (ScaleTab &t : c->scale_tabs)
+        if (t.d && !memcmp(t.key, key, sizeof key)) { t.used = c->scale_tick; *out = &t; return JMH_OK; }
+    if ((int)c->scale_tabs.size() < SCALE_TABS) {
+        c->scale_tabs.reserve(SCALE_TABS);               // entries are referred to by address
+        c->scale_tabs.emplace_back();
+        slot = &c->scale_tabs.back();
+    } else {
+        for (ScaleTab &t : c->scale_tabs) if (!slot || t.used < slot->used) slot = &t;
+        if (slot->up) HCHK(hipEventSynchronize(slot->up));
+        if (slot->d) HCHK(hipFreeAsync(slot->d, c->st));
+        slot->d = nullptr;
+    }
+    if (!slot->up && hipEventCreateWithFlags(&slot->up, hipEventDisableTiming) != hipSuccess) { slot->up = nullptr; return JMH_E_HIP; }
+    size_t end = 0;
+    std::vector<int32_t> first[2][2];
+    std::vector<int16_t> taps[2][2];
+    for (int pc = 0; pc < 2; pc++) {
+        const int ns[2] = {pc ? w / 2 : w, pc ? h / 2 : h}, nd[2] = {pc ? s.out_width / 2 : s.out_width, pc ? s.out_height / 2 : s.out_height};
+        for (int ax = 0; ax < 2; ax++) {
+            first[pc][ax].resize(nd[ax]);
+            taps[pc][ax].resize((size_t)nd[ax] * JMS_TAPS_MAX);
+            const int r = jms_taps(ns[ax], nd[ax], s.filter, pc && !ax && (s.flags & JMH_SCALE_CHROMA_LEFT), first[pc][ax].data(), taps[pc][ax].data(),
+                                   &slot->T[pc][ax]);
+            if (r) return r;
+        }
+        // the intermediate rows of k_scale's tallest tile fit its LDS (they do for every T <= JMS_TAPS_MAX)
+        if (jms_span(first[pc][1].data(), nd[1], slot->T[pc][1], pc ? c->H / 2 : c->H) > JMS_SPAN_MAX) return JMH_E_UNSUPPORTED_CFG;
+        const size_t bytes[4] = {(size_t)nd[0] * 4, (size_t)nd[1] * 4, (size_t)nd[0] * JMS_HPAIRS * 4, (size_t)nd[1] * JMS_VPAIRS * 4};
+        for (int i = 0; i < 4; i++) { slot->off[pc][i] = end; end += (bytes[i] + 15) & ~(size_t)15; }
+    }
+    slot->h.assign(end, 0);
+    for (int pc = 0; pc < 2; pc++) {
+        memcpy(slot->h.data() + slot->off[pc][0], first[pc][0].data(), first[pc][0].size() * 4);
+        memcpy(slot->h.data() + slot->off[pc][1], first[pc][1].data(), first[pc][1].size() * 4);
+        jms_pack_axis(first[pc][0].data(), taps[pc][0].data(), (int)first[pc][0].size(), slot->T[pc][0], 0, (uint32_t *)(slot->h.data() + slot->off[pc][2]));
+        jms_pack_axis(first[pc][1].data(), taps[pc][1].data(), (int)first[pc][1].size(), slot->T[pc][1], 1, (uint32_t *)(slot->h.data() + slot->off[pc][3]));
+    }
+    if (hipMallocAsync((void **)&slot->d, end, c->st) != hipSuccess) { slot->d = nullptr; return JMH_E_OOM; }
+    HCHK(hipMemcpyAsync(slot->d, slot->h.data(), end, hipMemcpyHostToDevice, c->st));
+    HCHK(hipEventRecord(slot->up, c->st));
+    memcpy(slot->key, key, sizeof key);
+    slot->used = c->scale_tick;
+    *out = slot;
+    return JMH_OK;
+}
+
+// With a scale set an ingest kernel packs its w x h source at its own size, rounded up to macroblocks, into the
+// context's scratch picture (scale_begin: where, and its size), and k_scale resamples that into dst (scale_end).
+// The scratch picture grows by a release and an allocation in stream order: behind its last reader
+static int scale_begin(jmh_ctx *c, int w, int h, uint8_t **out, int *W, int *H, ScaleTab **tab) {
+    int r = scale_tables(c, w, h, tab);
+    if (r) return r;
+    const int sW = (w + 15) & ~15, sH = (h + 15) & ~15;
+    const size_t need = (size_t)sW * sH * 3 / 2 * c->ps;
+    if (need > c->scl_cap) {
+        if (c->d_scl) HCHK(hipFreeAsync(c->d_scl, c->st));
+        c->d_scl = nullptr; c->scl_cap = 0;
+        if (hipMallocAsync((void **)&c->d_scl, need, c->st) != hipSuccess) { c->d_scl = nullptr; return JMH_E_OOM; }
+        c->scl_cap = need;
+    }
+    *out = c->d_scl; *W = sW; *H = sH;
+    return JMH_OK;
+}
+static int scale_end(jmh_ctx *c, const ScaleTab *t, int w, int h, int sW, int sH, uint8_t *dst) {
+    ScaleArgs a;
+    a.src = c->d_scl; a.dst = dst;
+    a.w = w; a.h = h; a.sW = sW; a.sH = sH; a.ow = t->key[2]; a.oh = t->key[3]; a.W = c->W; a.H = c->H;
+    for (int pc = 0; pc < 2; pc++) {
+        a.fh[pc] = (const int32_t *)(t->d + t->off[pc][0]); a.fv[pc] = (const int32_t *)(t->d + t->off[pc][1]);
+        a.th[pc] = (const uint32_t *)(t->d + t->off[pc][2]); a.tv[pc] = (const uint32_t *)(t->d + t->off[pc][3]);
+        a.nph[pc] = t->T[pc][0] / 2; a.npv[pc] = t->T[pc][1] / 2 + 1; a.tv_taps[pc] = t->T[pc][1];
+    }
+    a.maxv = c->maxv; a.P = 14 - c->bd;
+    HCHK(jmh_launch_scale(a, c->st));
     return JMH_OK;
 }
 
@@ -1261,13 +1378,17 @@ static int ingest_queue_tensor(jmh_ctx *c, const jmh_device_tensor *t, uint8_t *
         HCHK(hipEventRecord(ev, (hipStream_t)t->stream));
         HCHK(hipStreamWaitEvent(c->st, ev, 0));
     }
+    uint8_t *out = dst;
+    int W = c->W, H = c->H, r;
+    ScaleTab *tab = nullptr;
+    if (c->scale.filter != JMH_SCALE_OFF && (r = scale_begin(c, t->width, t->height, &out, &W, &H, &tab))) return r;
     TensorArgs g;
     for (int i = 0; i < 3; i++) g.chan[i] = (const uint8_t *)t->chan[i];
     g.sx = t->stride_x; g.sy = t->stride_y;
-    g.dst = dst; g.w = t->width; g.h = t->height; g.W = c->W; g.H = c->H;
+    g.dst = out; g.w = t->width; g.h = t->height; g.W = W; g.H = H;
     jmr_coefficients(t->flags, c->bd, &g.k);
     HCHK(jmh_launch_ingest_tensor(t->dtype, g, c->st));
-    return JMH_OK;
+    return tab ? scale_end(c, tab, t->width, t->height, W, H, dst) : JMH_OK;
 }
 
 // k_ingest of p into dst on the context's stream, behind the work queued on the caller's stream so
@@ -1277,17 +1398,21 @@ static int ingest_queue(jmh_ctx *c, const jmh_device_picture *p, uint8_t *dst, i
         HCHK(hipEventRecord(ev, (hipStream_t)p->stream));
         HCHK(hipStreamWaitEvent(c->st, ev, 0));
     }
+    uint8_t *out = dst;
+    int W = c->W, H = c->H, r;
+    ScaleTab *tab = nullptr;
+    if (c->scale.filter != JMH_SCALE_OFF && (r = scale_begin(c, p->width, p->height, &out, &W, &H, &tab))) return r;
     if (jmr_is_rgb(p->format)) {   // k_ingest_rgb: one plane, nothing counted
         RgbArgs g;
         g.src = (const uint8_t *)p->plane[0]; g.stride = p->stride[0];
-        g.dst = dst; g.w = p->width; g.h = p->height; g.W = c->W; g.H = c->H;
+        g.dst = out; g.w = p->width; g.h = p->height; g.W = W; g.H = H;
         jmr_coefficients(p->format, c->bd, &g.k);
         HCHK(jmh_launch_ingest_rgb(p->format, g, c->st));
-        return JMH_OK;
+        return tab ? scale_end(c, tab, p->width, p->height, W, H, dst) : JMH_OK;
     }
     IngestArgs a;
     for (int i = 0; i < 3; i++) { a.plane[i] = (const uint8_t *)p->plane[i]; a.stride[i] = p->stride[i]; }
-    a.dst = dst; a.w = p->width; a.h = p->height; a.W = c->W; a.H = c->H; a.maxv = (uint32_t)c->maxv; a.clamped = nullptr;
+    a.dst = out; a.w = p->width; a.h = p->height; a.W = W; a.H = H; a.maxv = (uint32_t)c->maxv; a.clamped = nullptr;
     const bool counts = p->format == JMH_PIX_I010;
     if (counts) {
         const size_t nb = (size_t)(c->nring + 1) * sizeof(unsigned long long);
@@ -1298,7 +1423,7 @@ static int ingest_queue(jmh_ctx *c, const jmh_device_picture *p, uint8_t *dst, i
     }
     HCHK(jmh_launch_ingest(p->format, a, c->st));
     if (counts) HCHK(hipMemcpyAsync(c->h_clamp + slot, a.clamped, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
-    return JMH_OK;
+    return tab ? scale_end(c, tab, p->width, p->height, W, H, dst) : JMH_OK;
 }
 
 static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *fp, const CodedPush *cp = nullptr) {
@@ -1783,6 +1908,24 @@ static int load_frame_any(jmh_ctx *c, int slot, const void *y, const void *u, co
     if (!pack_planes(c->h_stage_ref, c->W, c->H, y, u, v, sy, sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
     HCHK(hipMemcpyAsync(c->d_slots + (size_t)slot * c->fsize, c->h_stage_ref, c->fsize, hipMemcpyHostToDevice, c->st));
     HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+
+// jmhip_scale.h: the sticky setting of the device pushes, its tables on the host, the setting read back
+extern "C" int jmh_input_scale(jmh_ctx *c, const jmh_scale *s) {
+    if (!c) return JMH_E_INVALID_ARG;
+    if (!s || s->filter == JMH_SCALE_OFF) { c->scale = jmh_scale{0, 0, 0, 0}; return JMH_OK; }
+    if (jms_check_setting(s->filter, s->flags, s->out_width, s->out_height, c->W, c->H)) return JMH_E_INVALID_ARG;
+    c->scale = *s;
+    return JMH_OK;
+}
+extern "C" int jmh_scale_taps(int n_src, int n_dst, int filter, int chroma_left, int32_t *first, int16_t *taps, int *ntaps) {
+    return jms_taps(n_src, n_dst, filter, chroma_left != 0, first, taps, ntaps);
+}
+extern "C" int jmh_scale_info(const jmh_ctx *c, jmh_scale *s, int *active) {
+    if (!c || !s || !active) return JMH_E_INVALID_ARG;
+    *s = c->scale;
+    *active = c->scale.filter != JMH_SCALE_OFF;
     return JMH_OK;
 }
 

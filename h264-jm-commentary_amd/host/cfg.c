@@ -75,6 +75,10 @@ static const map_entry Map[] = {
     {"DeviceInputMatrix", 0, OFF(device_input_matrix), 0, 1},
     {"DeviceInputFullRange", 0, OFF(device_input_full), 0, 1},
     {"DeviceInputTensor", 0, OFF(device_input_tensor), 0, 4},
+    {"DeviceInputScale", 0, OFF(device_input_scale), 0, 3},
+    {"DeviceInputWidth", 0, OFF(device_input_width), 0, 65536},
+    {"DeviceInputHeight", 0, OFF(device_input_height), 0, 65536},
+    {"DeviceInputChromaLeft", 0, OFF(device_input_chroma_left), 0, 1},
     {"DeviceReconFormat", 0, OFF(device_recon_format), 0, 19},
     {"DeviceReconTensor", 0, OFF(device_recon_tensor), 0, 4},
     {"DeviceReconMatrix", 0, OFF(device_recon_matrix), 0, 1},
@@ -201,6 +205,9 @@ jm_device_push_rgb_fn jm_device_input_rgb(void) { return device_input_rgb_fn; }
 static jm_device_push_tensor_fn device_input_tensor_fn;
 void jm_set_device_input_tensor(jm_device_push_tensor_fn fn) { device_input_tensor_fn = fn; }
 jm_device_push_tensor_fn jm_device_input_tensor(void) { return device_input_tensor_fn; }
+static jm_device_scale_fn device_input_scale_fn;
+void jm_set_device_input_scale(jm_device_scale_fn fn) { device_input_scale_fn = fn; }
+jm_device_scale_fn jm_device_input_scale(void) { return device_input_scale_fn; }
 static jm_device_output_fn device_output_fn;
 void jm_set_device_output(jm_device_output_fn fn) { device_output_fn = fn; }
 jm_device_output_fn jm_device_output(void) { return device_output_fn; }
@@ -234,6 +241,13 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->device_input_tensor == 4 && inp->bit_depth_luma != 8 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputTensor=4 (gbrpf32le) is quantised to 8 or 10 bits: it needs SourceBitDepthLuma=8 or 10 (got %d)", inp->bit_depth_luma); return -1; }
     if (inp->device_input_tensor && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV (InputFile=%s)", inp->device_input_tensor, inp->infile); return -1; }
     if (inp->device_input_tensor && !inp->device_writer_async) { snprintf(err, errlen, "DeviceInputTensor=%d leaves no YUV source on the host, so the distortion comes from the device's SSDs: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1)", inp->device_input_tensor); return -1; }
+    if (!inp->device_input_scale && (inp->device_input_width || inp->device_input_height || inp->device_input_chroma_left)) { snprintf(err, errlen, "DeviceInputWidth / DeviceInputHeight / DeviceInputChromaLeft describe a source the device scales: they need DeviceInputScale=1..3"); return -1; }
+    if (inp->device_input_scale && !inp->device_input) { snprintf(err, errlen, "DeviceInputScale=%d scales a picture pushed from device memory: it needs DeviceInput=1", inp->device_input_scale); return -1; }
+    if (inp->device_input_scale && !device_input_scale_fn) { snprintf(err, errlen, "DeviceInputScale=%d scales the source on the device: it needs the device backend (this build has no device scaler: DeviceInputScale=0)", inp->device_input_scale); return -1; }
+    if (inp->device_input_scale && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputScale=%d reads frames of DeviceInputWidth x DeviceInputHeight from InputFile: the synthetic source has the coded size (InputFile=%s)", inp->device_input_scale, inp->infile); return -1; }
+    if (inp->device_input_scale && !inp->device_writer_async) { snprintf(err, errlen, "DeviceInputScale=%d leaves no source of the coded size on the host, so the distortion comes from the device's SSDs: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1)", inp->device_input_scale); return -1; }
+    if (inp->device_input_scale && (inp->device_input_width < 2 || inp->device_input_height < 2 || inp->device_input_width > 8192 || inp->device_input_height > 8192)) { snprintf(err, errlen, "DeviceInputScale=%d: DeviceInputWidth=%d DeviceInputHeight=%d out of range (the frame size of InputFile, 2..8192)", inp->device_input_scale, inp->device_input_width, inp->device_input_height); return -1; }
+    if (inp->device_input_scale && ((inp->device_input_width | inp->device_input_height | inp->width | inp->height) & 1)) { snprintf(err, errlen, "DeviceInputScale=%d: DeviceInputWidth=%d DeviceInputHeight=%d SourceWidth=%d SourceHeight=%d must be even (4:2:0 planes of half size are scaled)", inp->device_input_scale, inp->device_input_width, inp->device_input_height, inp->width, inp->height); return -1; }
     if (inp->device_recon_format && inp->device_recon_tensor) { snprintf(err, errlen, "DeviceReconFormat=%d and DeviceReconTensor=%d both name the layout of ReconFile: set one of them", inp->device_recon_format, inp->device_recon_tensor); return -1; }
     if (inp->device_recon_format && inp->device_recon_format < 16) { snprintf(err, errlen, "DeviceReconFormat=%d not supported (0: YUV, 16 BGRA8, 17 RGBA8, 18 RGB10A2, 19 BGR10A2)", inp->device_recon_format); return -1; }
     if ((inp->device_recon_matrix || inp->device_recon_full) && !inp->device_recon_format && !inp->device_recon_tensor) { snprintf(err, errlen, "DeviceReconMatrix / DeviceReconFullRange describe an RGB ReconFile: they need DeviceReconFormat=16..19 or DeviceReconTensor=1..4"); return -1; }

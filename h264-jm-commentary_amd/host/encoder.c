@@ -456,6 +456,14 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fprintf(stderr, "DeviceInputTensor=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n", tensor_kind);
         return JMH_E_UNSUPPORTED_CFG;
     }
+    const int scale = inp->device_input_scale;
+    const jm_device_scale_fn device_scale_fn = scale ? jm_device_input_scale() : NULL;
+    if (scale && (!device_input_fn || !device_scale_fn || !inp->device_writer_async)) {
+        fprintf(stderr, "DeviceInputScale=%d needs DeviceInput=1 and DeviceWriterAsync=1 on the device backend (backend '%s')\n", scale, be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
+    /* the frames of InputFile: DeviceInputWidth x DeviceInputHeight under DeviceInputScale, else the display size */
+    const int src_w = scale ? inp->device_input_width : inp->width, src_h = scale ? inp->device_input_height : inp->height;
     if (inp->device_writer_async && !(device_coded_push_fn && device_coded_pop_fn)) {
         fprintf(stderr, "DeviceWriterAsync=1 needs the device backend (backend '%s' has no coded push / pop: DeviceWriterAsync=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
@@ -487,6 +495,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     int synthetic = !strncmp(inp->infile, "synthetic:", 10);
     if (synthetic && rgb_format) { fprintf(stderr, "DeviceInputFormat=%d reads RGB frames from InputFile: the synthetic source is YUV\n", inp->device_input_format); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic && tensor_kind) { fprintf(stderr, "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV\n", tensor_kind); return JMH_E_UNSUPPORTED_CFG; }
+    if (synthetic && scale) { fprintf(stderr, "DeviceInputScale=%d reads frames of DeviceInputWidth x DeviceInputHeight from InputFile: the synthetic source has the coded size\n", scale); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic) seed = strtoull(inp->infile + 10, NULL, 10);
     else if (!(fin = fopen(inp->infile, "rb"))) { fprintf(stderr, "Input file %s does not exist\n", inp->infile); return JMH_E_INVALID_ARG; }
     if (!(fout = fopen(inp->outfile, "wb"))) { fprintf(stderr, "Cannot open output file %s\n", inp->outfile); if (fin) fclose(fin); return JMH_E_INVALID_ARG; }
@@ -541,15 +550,19 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     /* DeviceInputFormat: one frame as read, height rows of 4 * width bytes (free again when its upload returns);
        DeviceInputTensor: one frame of its file, in the same buffer */
     const int raw_source = rgb_format || tensor_kind;
-    const size_t rgb_bytes = tensor_kind ? jm_tensor_frame_bytes(tensor_kind, inp->width, inp->height) : (size_t)4 * inp->width * inp->height;
+    const size_t rgb_bytes = tensor_kind ? jm_tensor_frame_bytes(tensor_kind, src_w, src_h) : (size_t)4 * src_w * src_h;
     uint8_t *rgb = raw_source ? (uint8_t *)malloc(rgb_bytes) : NULL;
-    int alloc_fail = !pend || (raw_source && !rgb) || jm_pic_alloc_bd(&rec, W, H, bd);
+    /* DeviceInputScale with a YUV file: one frame as read, at its own size (free again when its upload returns) */
+    jm_pic big;
+    memset(&big, 0, sizeof(big));
+    int alloc_fail = !pend || (raw_source && !rgb) || jm_pic_alloc_bd(&rec, W, H, bd) || (scale && !raw_source && jm_pic_alloc_bd(&big, src_w, src_h, bd));
     for (int k = 0; k < plen && !alloc_fail; k++) alloc_fail = jm_pic_alloc_bd(&pend[k].cur, W, H, bd);
     if (alloc_fail) {
         if (pend) for (int k = 0; k < plen; k++) jm_pic_free(&pend[k].cur);
         free(pend);
         free(rgb);
         jm_pic_free(&rec);
+        jm_pic_free(&big);
         if (fin) fclose(fin);
         fclose(fout);
         if (frec) fclose(frec);
@@ -630,10 +643,17 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
                     drec.tensor == 1 ? "rgb24" : drec.tensor == 2 ? "gbrp" : drec.tensor == 3 ? "gbrp10le" : drec.tensor == 4 ? "gbrpf32le"
                     : inp->device_recon_format == 16 ? "16" : inp->device_recon_format == 17 ? "17" : inp->device_recon_format == 18 ? "18" : "19",
                     inp->device_recon_matrix ? "709" : "601", inp->device_recon_full ? "full" : "limited");
+        if (scale)
+            fprintf(log, " (the source has %dx%d samples: resampled on the device to %dx%d, %s, chroma %s)\n", src_w, src_h, inp->width, inp->height,
+                    scale == 1 ? "bilinear" : scale == 2 ? "bicubic" : "Lanczos3", inp->device_input_chroma_left ? "left-sited" : "centred");
         if (device_input_fn) fprintf(log, " (the source is uploaded as read and pushed from device memory: the device pads it to the coded size)\n");
         if (async) fprintf(log, " (the slice writer is queued behind each picture: its pop returns the slice bytes and the SSDs)\n");
         if (nal) fprintf(log, " (NAL units finished on the device: the pop returns the picture's access unit)\n");
         fprintf(log, " Frame  Bit/pic  QP   SnrY    SnrU    SnrV    Time(ms) MET(ms) Frm/Fld  I D\n");
+    }
+    if (scale) {                                 /* once, before the first picture: every push follows it */
+        const int r = device_scale_fn(be->ctx, scale, inp->device_input_chroma_left ? JMH_SCALE_CHROMA_LEFT : 0, inp->width, inp->height);
+        if (r) { fprintf(stderr, "DeviceInputScale=%d to %dx%d: the backend refused it (%d)\n", scale, inp->width, inp->height, r); st_ret = r; goto cleanup; }
     }
     double t_start = now_ms();
     int frame_num = 0, head = 0, count = 0;
@@ -789,7 +809,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             if (fseek(fin, (long)rgb_bytes * idx, SEEK_SET) || fread(rgb, 1, rgb_bytes, fin) != rgb_bytes) { fprintf(stderr, "ReadOneFrame: cannot read RGB frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
         } else
         if (synthetic) jm_synth_frame(&p->cur, inp->width, inp->height, seed, idx);
-        else if (jm_read_yuv_frame(fin, &p->cur, inp->width, inp->height, idx)) { fprintf(stderr, "ReadOneFrame: cannot read frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
+        else if (jm_read_yuv_frame(fin, scale ? &big : &p->cur, src_w, src_h, idx)) { fprintf(stderr, "ReadOneFrame: cannot read frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
         read_ms += now_ms() - tr;
         p->f = f;
         p->is_i = f == 0 || (inp->intra_period && f % inp->intra_period == 0);
@@ -816,9 +836,9 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             PEND_SLICE(p, sl);
             device_slice_headers(d, &s, &sl);
             if (nal && !(r = device_slice_heads(d, &sl))) r = device_nal_fn(be->ctx, d->n, d->nh);
-            if (!r) r = tensor_kind ? device_input_tensor_fn(be->ctx, rgb, tensor_kind, tensor_flags, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
-                  : rgb_format ? device_input_rgb_fn(be->ctx, rgb, rgb_format, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
-                  : device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, d->n, d->cs, inp->width, inp->height)
+            if (!r) r = tensor_kind ? device_input_tensor_fn(be->ctx, rgb, tensor_kind, tensor_flags, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
+                  : rgb_format ? device_input_rgb_fn(be->ctx, rgb, rgb_format, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
+                  : device_input_fn ? device_input_fn(be->ctx, scale ? &big : &p->cur, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
                                 : device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
         } else
         if (!r) r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, 0, NULL, 0, 0)
@@ -905,6 +925,7 @@ cleanup:
     free(pend);
     free(rgb);
     jm_pic_free(&rec);
+    jm_pic_free(&big);
     if (fin) fclose(fin);
     fclose(fout);
     if (frec) fclose(frec);

@@ -100,6 +100,14 @@ typedef struct jm_input {
                                   planes; 8- or 10-bit).  A frame is uploaded raw and pushed as a device tensor
                                   (include/jmhip_tensor.h); DeviceInputMatrix / DeviceInputFullRange apply.  0: off.
                                   Needs DeviceWriterAsync 1; excludes DeviceInputFormat                      */
+    int  device_input_scale;   /* (this build) DeviceInputScale 1..3: with DeviceInput 1 the frames of InputFile have
+                                  DeviceInputWidth x DeviceInputHeight samples (even, 2..8192) and the device
+                                  resamples each to SourceWidth x SourceHeight, which stay the output / display
+                                  size: 1 bilinear, 2 bicubic, 3 Lanczos3 (jmh_input_scale of
+                                  include/jmhip_scale.h).  Combines with DeviceInputFormat / DeviceInputTensor.
+                                  Needs DeviceWriterAsync 1 (no source of the coded size on the host).  0: off */
+    int  device_input_width, device_input_height;
+    int  device_input_chroma_left;   /* (this build) DeviceInputChromaLeft 1: 4:2:0 chroma is left-sited (0: centred) */
     int  device_recon_format;  /* (this build) DeviceReconFormat 16..19: ReconFile holds the display-size picture
                                   converted on the device to packed RGB (height rows of 4 * width bytes, the
                                   layouts of DeviceInputFormat; jmh_pull_picture of include/jmhip_output.h) and
@@ -306,6 +314,12 @@ typedef int (*jm_device_push_tensor_fn)(void *ctx, const void *frame, int kind, 
                                         int n, const jmh_coded_slice *slices, int crop_w, int crop_h);
 void jm_set_device_input_tensor(jm_device_push_tensor_fn fn);
 jm_device_push_tensor_fn jm_device_input_tensor(void);
+/* DeviceInputScale 1..3: the backend's sticky scale of its device pushes (jmh_input_scale, include/jmhip_scale.h):
+   every push that follows takes a source of any even size and resamples it to out_w x out_h.  Registered before
+   jm_configure: PatchInp rejects the keys on a backend without one */
+typedef int (*jm_device_scale_fn)(void *ctx, int filter, int flags, int out_w, int out_h);
+void jm_set_device_input_scale(jm_device_scale_fn fn);
+jm_device_scale_fn jm_device_input_scale(void);
 /* DeviceReconFormat 16..19 / DeviceReconTensor 1..4: the backend's pull of the current picture, deblocked, at the
    display size into dst on the host (jmh_pull_picture / jmh_pull_tensor, then jmh_device_download): format with
    its flags and tensor 0, or format 0, tensor 1..4 and flags.  dst holds jm_recon_frame_bytes bytes.  Registered

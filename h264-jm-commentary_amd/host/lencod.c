@@ -171,6 +171,11 @@ static int gpu_pull_recon(void *ctx, int format, int tensor, int flags, int dw, 
     }
     return r ? r : jmh_device_download((jmh_ctx *)ctx, dst, gpu_out.buf, bytes, gpu_out.stream);
 }
+/* DeviceInputScale 1..3: the sticky setting of the pushes above */
+static int gpu_input_scale(void *ctx, int filter, int flags, int ow, int oh) {
+    const jmh_scale s = {filter, flags, ow, oh};
+    return jmh_input_scale((jmh_ctx *)ctx, &s);
+}
 static void gpu_input_release(void *ctx) {
     if (gpu_in.stream) (void)jmh_device_stream_destroy((jmh_ctx *)ctx, gpu_in.stream);
     if (gpu_in.buf) (void)jmh_device_free((jmh_ctx *)ctx, gpu_in.buf);
@@ -187,6 +192,7 @@ int main(int argc, char **argv) {
     jm_set_device_input(gpu_push_device);   /* before PatchInp: it rejects DeviceInput on a backend without one */
     jm_set_device_input_rgb(gpu_push_device_rgb);
     jm_set_device_input_tensor(gpu_push_device_tensor);
+    jm_set_device_input_scale(gpu_input_scale);
     jm_set_device_output(gpu_pull_recon);
     if (jm_configure(&inp, argc, argv, err, sizeof(err))) { fprintf(stderr, "%s\n", err); return 1; }
     jmh_config cfg;

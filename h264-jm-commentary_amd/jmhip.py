@@ -336,12 +336,43 @@ _SIGS_OUTPUT = {
 }
 EXPORTED_OUTPUT = tuple(_SIGS_OUTPUT)
 
+# ---- device pushes scaled to a chosen size (include/jmhip_scale.h; additive to ABI 14) ----
+JMH_SCALE_OFF, JMH_SCALE_BILINEAR, JMH_SCALE_BICUBIC, JMH_SCALE_LANCZOS3 = 0, 1, 2, 3
+JMH_SCALE_CHROMA_LEFT = 1
+JMH_SCALE_TAPS_MAX, JMH_SCALE_SRC_MAX = 24, 8192
+
+
+class JmhScale(ctypes.Structure):
+    _fields_ = [("filter", ctypes.c_int32), ("flags", ctypes.c_int32), ("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32)]
+
+
+_SIGS_SCALE = {
+    "jmh_input_scale": (_I, [_P, _P]),
+    "jmh_scale_taps": (_I, [_I, _I, _I, _I, _P, _P, _P]),
+    "jmh_scale_info": (_I, [_P, _P, _P]),
+}
+EXPORTED_SCALE = tuple(_SIGS_SCALE)
+
 # ---- the unit seam of the searches' spiral decode (include/jmhip_spiral.h; additive to ABI 14);
 #      bound where it is called (Encoder.spiral_positions), so that a library built before it loads
 _SIGS_SPIRAL = {
     "jmh_spiral_positions": (_I, [_P, _I, _P]),
 }
 EXPORTED_SPIRAL = tuple(_SIGS_SPIRAL)
+
+
+def scale_taps(n_src, n_dst, filter, chroma_left=False):
+    """jmh_scale_taps: the tap tables of one axis of the scaler (include/jmhip_scale.h) as (first, taps):
+    first[n_dst] int32, unclamped, and taps[n_dst, T] int16, every row summing to 16384.  Needs no
+    device.  More than JMH_SCALE_TAPS_MAX taps: JmhError with status JMH_E_UNSUPPORTED_CFG."""
+    lib = load()
+    nt = ctypes.c_int(0)
+    st = lib.jmh_scale_taps(n_src, n_dst, filter, int(bool(chroma_left)), None, None, ctypes.byref(nt))
+    _check(st, "jmh_scale_taps")
+    first = np.empty(n_dst, np.int32)
+    taps = np.empty((n_dst, nt.value), np.int16)
+    _check(lib.jmh_scale_taps(n_src, n_dst, filter, int(bool(chroma_left)), _ptr(first), _ptr(taps), ctypes.byref(nt)), "jmh_scale_taps")
+    return first, taps
 
 
 def rgb_coefficients(format, bit_depth):
@@ -760,7 +791,7 @@ def load(path=LIB_PATH):
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(_SIGS.items()) + list(_SIGS_CAVLC.items()) + list(_SIGS_CABAC.items()) + list(_SIGS_CODED.items()) + \
             list(_SIGS_CABAC_SPLIT.items()) + list(_SIGS_INPUT.items()) + list(_SIGS_NAL.items()) + list(_SIGS_RGB.items()) + list(_SIGS_TENSOR.items()) + \
-            list(_SIGS_OUTPUT.items()):
+            list(_SIGS_OUTPUT.items()) + list(_SIGS_SCALE.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1050,6 +1081,26 @@ class Encoder:
         s = pic.struct()
         _check(self.lib.jmh_ingest_picture(self.ctx, ctypes.byref(s), _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2), "jmh_ingest_picture")
         return y, u, v
+
+    # ---- device pushes scaled to a chosen size (include/jmhip_scale.h) ----
+    def input_scale(self, out_w, out_h=None, filter=JMH_SCALE_LANCZOS3, chroma_left=False):
+        """jmh_input_scale: from now on every device push and unit seam (pictures, RGB, tensors) takes a
+        source of any even size up to JMH_SCALE_SRC_MAX, resamples it to out_w x out_h (even, at most
+        the coded size) and pads that to the coded size.  input_scale(None) turns it off.  Pictures
+        already pushed keep the setting of their push."""
+        if out_w is None:
+            _check(self.lib.jmh_input_scale(self.ctx, None), "jmh_input_scale")
+            return
+        s = JmhScale(filter, JMH_SCALE_CHROMA_LEFT if chroma_left else 0, out_w, out_h)
+        _check(self.lib.jmh_input_scale(self.ctx, ctypes.byref(s)), "jmh_input_scale")
+
+    def scale_info(self):
+        """jmh_scale_info: the current setting as a dict, or None when it is off."""
+        s, on = JmhScale(), ctypes.c_int(0)
+        _check(self.lib.jmh_scale_info(self.ctx, ctypes.byref(s), ctypes.byref(on)), "jmh_scale_info")
+        if not on.value:
+            return None
+        return {"filter": s.filter, "chroma_left": bool(s.flags & JMH_SCALE_CHROMA_LEFT), "out_width": s.out_width, "out_height": s.out_height}
 
     # ---- tensors that are already on the device (include/jmhip_tensor.h) ----
     def device_tensor(self, layout, stream=None, base=None):

@@ -388,5 +388,6 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #include "jmhip_rgb.h"
 #include "jmhip_tensor.h"
 #include "jmhip_spiral.h"
+#include "jmhip_scale.h"
 #include "jmhip_output.h"
 #endif /* JMHIP_H */
