@@ -292,6 +292,16 @@ struct RgbArgs {
     jmr_coef k;                          // the conversion of the format's flags at the context's bit depth
 };
 
+// k_ingest_yuv (jmh_yuv.hip): a 4:2:2 or 4:4:4 device picture of w x h luma samples reduced into the packed W x H source
+struct YuvArgs {
+    const uint8_t *plane[3];             // device planes of the caller (jmhip_yuv.h), those the layout reads
+    int64_t stride[3];                   // bytes per row
+    uint8_t *dst;                        // Y, U, V of the coded size, samples of 1 or 2 bytes
+    int w, h, W, H;
+    uint32_t maxv;
+    unsigned long long *clamped;         // I210, I410: samples above maxv are added here
+};
+
 // k_ingest_tensor (jmh_tensor.hip): a device tensor of w x h pixels quantised and converted into the packed W x H source
 struct TensorArgs {
     const uint8_t *chan[3];              // R, G, B of the caller (jmhip_tensor.h) at pixel (0, 0)

@@ -15,6 +15,7 @@ hipError_t jmh_launch_rdo(const TickArgs &t, hipStream_t st, hipStream_t side, h
 size_t jmh_rdo_scratch_bytes();
 hipError_t jmh_launch_ingest(int format, const IngestArgs &a, hipStream_t st);      // jmh_ingest.hip
 hipError_t jmh_launch_ingest_rgb(int format, const RgbArgs &a, hipStream_t st);    // jmh_rgb.hip
+hipError_t jmh_launch_ingest_yuv(int format, const YuvArgs &a, hipStream_t st);    // jmh_yuv.hip
 hipError_t jmh_launch_ingest_tensor(int dtype, const TensorArgs &a, hipStream_t st);   // jmh_tensor.hip
 hipError_t jmh_launch_scale(const ScaleArgs &a, hipStream_t st);                         // jmh_scale.hip
 hipError_t jmh_launch_pull_picture(int format, const OutArgs &a, hipStream_t st);      // jmh_output.hip

@@ -26,6 +26,7 @@
 #include "jmh_ingest.h"
 #include "jmh_scale.h"
 #include "jmh_rgb.h"
+#include "jmh_yuv.h"
 #include "jmh_tensor.h"
 #include "jmh_output.h"
 #include "jmh_nal.h"
@@ -182,6 +183,9 @@ enum { REF_NONE, REF_BUF, REF_REC, REF_DBK };
 
 static_assert(JMS_INVALID == JMH_E_INVALID_ARG && JMS_UNSUPPORTED == JMH_E_UNSUPPORTED_CFG && JMS_TAPS_MAX == JMH_SCALE_TAPS_MAX &&
               JMS_SRC_MAX == JMH_SCALE_SRC_MAX && JMS_LANCZOS3 == JMH_SCALE_LANCZOS3 && JMS_CHROMA_LEFT == JMH_SCALE_CHROMA_LEFT, "jmh_scale.h restates jmhip_scale.h");
+static_assert(JMY_I422 == JMH_PIX_I422 && JMY_NV16 == JMH_PIX_NV16 && JMY_YUYV == JMH_PIX_YUYV && JMY_UYVY == JMH_PIX_UYVY && JMY_I444 == JMH_PIX_I444 &&
+              JMY_VUYA8 == JMH_PIX_VUYA8 && JMY_I210 == JMH_PIX_I210 && JMY_P210 == JMH_PIX_P210 && JMY_Y210 == JMH_PIX_Y210 && JMY_I410 == JMH_PIX_I410 &&
+              JMY_Y410 == JMH_PIX_Y410 && JMY_CHROMA_LEFT == JMH_PIX_CHROMA_LEFT, "jmh_yuv.h restates jmhip_yuv.h");
 // the tables of one geometry of the scaler (jmh_scale.h, jms_pack_axis) on the device; h: what was uploaded, kept
 // while the copy may be pending (up)
 #define SCALE_TABS 8
@@ -1267,17 +1271,23 @@ static int alloc_coded(jmh_ctx *c, PicBuf &b) {
 // the source of a pushed picture: host planes (strides in samples), a device picture or a device tensor
 struct PushSrc { const void *y, *u, *v; int sy, sc; bool wide; const jmh_device_picture *dev; const jmh_device_tensor *ten; };
 
-// the argument rules of jmhip_input.h (formats 0..3, no flag) and of jmhip_rgb.h (16..19 with their flags)
+// the argument rules of jmhip_input.h (formats 0..3, no flag), of jmhip_rgb.h (16..19 with their flags) and of
+// jmhip_yuv.h (32..37 and 40..44 with their flag)
 static int check_device_pic(const jmh_ctx *c, const jmh_device_picture *p) {
     if (!p) return JMH_E_INVALID_ARG;
     const bool sc = c->scale.filter != JMH_SCALE_OFF;   // the source bound is the scaler's, not the coded size
     const int BW = sc ? JMS_SRC_MAX : c->W, BH = sc ? JMS_SRC_MAX : c->H;
-    if (jmr_is_rgb(p->format) ? jmr_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)
-                              : jmi_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)) return JMH_E_INVALID_ARG;
+    if (jmr_is_rgb(p->format)   ? jmr_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)
+        : jmy_is_yuv(p->format) ? jmy_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)
+                                : jmi_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)) return JMH_E_INVALID_ARG;
     return sc ? jms_check(p->width, p->height, c->scale.out_width, c->scale.out_height, c->scale.filter) : JMH_OK;
 }
 // whether a context of this bit depth takes the (checked) format
-static bool device_depth_ok(const jmh_ctx *c, int format) { return jmr_is_rgb(format) ? jmr_depth_ok(format, c->bd) : jmi_depth_ok(format, c->bd); }
+static bool device_depth_ok(const jmh_ctx *c, int format) {
+    return jmr_is_rgb(format) ? jmr_depth_ok(format, c->bd) : jmy_is_yuv(format) ? jmy_depth_ok(format, c->bd) : jmi_depth_ok(format, c->bd);
+}
+// whether the packing kernel of the (checked) format counts samples above maxv (jmh_device_input_clamped)
+static bool device_format_counts(int format) { return format == JMH_PIX_I010 || (jmy_is_yuv(format) && jmy_clamps(jmy_layout(format))); }
 
 // the argument rules of jmhip_tensor.h
 static int check_device_tensor(const jmh_ctx *c, const jmh_device_tensor *t) {
@@ -1410,19 +1420,30 @@ static int ingest_queue(jmh_ctx *c, const jmh_device_picture *p, uint8_t *dst, i
         HCHK(jmh_launch_ingest_rgb(p->format, g, c->st));
         return tab ? scale_end(c, tab, p->width, p->height, W, H, dst) : JMH_OK;
     }
-    IngestArgs a;
-    for (int i = 0; i < 3; i++) { a.plane[i] = (const uint8_t *)p->plane[i]; a.stride[i] = p->stride[i]; }
-    a.dst = out; a.w = p->width; a.h = p->height; a.W = W; a.H = H; a.maxv = (uint32_t)c->maxv; a.clamped = nullptr;
-    const bool counts = p->format == JMH_PIX_I010;
+    unsigned long long *clamped = nullptr;
+    const bool counts = device_format_counts(p->format);
     if (counts) {
         const size_t nb = (size_t)(c->nring + 1) * sizeof(unsigned long long);
         if (!c->d_clamp && hipMalloc((void **)&c->d_clamp, nb) != hipSuccess) { c->d_clamp = nullptr; return JMH_E_OOM; }
         if (!c->h_clamp && hipHostMalloc((void **)&c->h_clamp, nb, hipHostMallocDefault) != hipSuccess) { c->h_clamp = nullptr; return JMH_E_OOM; }
-        a.clamped = c->d_clamp + slot;
-        HCHK(hipMemsetAsync(a.clamped, 0, sizeof(unsigned long long), c->st));
+        clamped = c->d_clamp + slot;
+        HCHK(hipMemsetAsync(clamped, 0, sizeof(unsigned long long), c->st));
     }
-    HCHK(jmh_launch_ingest(p->format, a, c->st));
-    if (counts) HCHK(hipMemcpyAsync(c->h_clamp + slot, a.clamped, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
+    if (jmy_is_yuv(p->format)) {   // k_ingest_yuv: 4:2:2 / 4:4:4 reduced to 4:2:0 (planes the layout does not read stay null)
+        YuvArgs g;
+        for (int i = 0; i < 3; i++) {
+            const bool read = i < jmy_planes(jmy_layout(p->format));
+            g.plane[i] = read ? (const uint8_t *)p->plane[i] : nullptr; g.stride[i] = read ? p->stride[i] : 0;
+        }
+        g.dst = out; g.w = p->width; g.h = p->height; g.W = W; g.H = H; g.maxv = (uint32_t)c->maxv; g.clamped = clamped;
+        HCHK(jmh_launch_ingest_yuv(p->format, g, c->st));
+    } else {
+        IngestArgs a;
+        for (int i = 0; i < 3; i++) { a.plane[i] = (const uint8_t *)p->plane[i]; a.stride[i] = p->stride[i]; }
+        a.dst = out; a.w = p->width; a.h = p->height; a.W = W; a.H = H; a.maxv = (uint32_t)c->maxv; a.clamped = clamped;
+        HCHK(jmh_launch_ingest(p->format, a, c->st));
+    }
+    if (counts) HCHK(hipMemcpyAsync(c->h_clamp + slot, clamped, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
     return tab ? scale_end(c, tab, p->width, p->height, W, H, dst) : JMH_OK;
 }
 
@@ -1613,7 +1634,7 @@ static void pop_done(jmh_ctx *c, int e) {
     c->popq.pop_front();
     c->ring[e].unpopped = 0;
     c->cur_entry = e;
-    c->last_clamped = c->ring[e].dev_fmt == JMH_PIX_I010 + 1 ? c->h_clamp[e] : 0;
+    c->last_clamped = c->ring[e].dev_fmt && device_format_counts(c->ring[e].dev_fmt - 1) ? c->h_clamp[e] : 0;
     float ms = 0;
     if (hipEventElapsedTime(&ms, c->ring[e].ev_t0, c->ring[e].ev_done) == hipSuccess) c->timing.total_ms = ms;
 }
@@ -1951,7 +1972,7 @@ extern "C" int jmh_ingest_picture(jmh_ctx *c, const jmh_device_picture *pic, voi
     std::vector<uint8_t> h(c->fsize);
     HCHK(hipMemcpy(h.data(), d, c->fsize, hipMemcpyDeviceToHost));
     unpack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps);
-    c->last_clamped = pic->format == JMH_PIX_I010 ? c->h_clamp[c->nring] : 0;
+    c->last_clamped = device_format_counts(pic->format) ? c->h_clamp[c->nring] : 0;
     return JMH_OK;
 }
 

@@ -79,6 +79,7 @@ static const map_entry Map[] = {
     {"DeviceInputWidth", 0, OFF(device_input_width), 0, 65536},
     {"DeviceInputHeight", 0, OFF(device_input_height), 0, 65536},
     {"DeviceInputChromaLeft", 0, OFF(device_input_chroma_left), 0, 1},
+    {"DeviceInputYUV", 0, OFF(device_input_yuv), 0, 44},
     {"DeviceReconFormat", 0, OFF(device_recon_format), 0, 19},
     {"DeviceReconTensor", 0, OFF(device_recon_tensor), 0, 4},
     {"DeviceReconMatrix", 0, OFF(device_recon_matrix), 0, 1},
@@ -205,6 +206,9 @@ jm_device_push_rgb_fn jm_device_input_rgb(void) { return device_input_rgb_fn; }
 static jm_device_push_tensor_fn device_input_tensor_fn;
 void jm_set_device_input_tensor(jm_device_push_tensor_fn fn) { device_input_tensor_fn = fn; }
 jm_device_push_tensor_fn jm_device_input_tensor(void) { return device_input_tensor_fn; }
+static jm_device_push_rgb_fn device_input_yuv_fn;
+void jm_set_device_input_yuv(jm_device_push_rgb_fn fn) { device_input_yuv_fn = fn; }
+jm_device_push_rgb_fn jm_device_input_yuv(void) { return device_input_yuv_fn; }
 static jm_device_scale_fn device_input_scale_fn;
 void jm_set_device_input_scale(jm_device_scale_fn fn) { device_input_scale_fn = fn; }
 jm_device_scale_fn jm_device_input_scale(void) { return device_input_scale_fn; }
@@ -241,7 +245,17 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->device_input_tensor == 4 && inp->bit_depth_luma != 8 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputTensor=4 (gbrpf32le) is quantised to 8 or 10 bits: it needs SourceBitDepthLuma=8 or 10 (got %d)", inp->bit_depth_luma); return -1; }
     if (inp->device_input_tensor && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV (InputFile=%s)", inp->device_input_tensor, inp->infile); return -1; }
     if (inp->device_input_tensor && !inp->device_writer_async) { snprintf(err, errlen, "DeviceInputTensor=%d leaves no YUV source on the host, so the distortion comes from the device's SSDs: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1)", inp->device_input_tensor); return -1; }
-    if (!inp->device_input_scale && (inp->device_input_width || inp->device_input_height || inp->device_input_chroma_left)) { snprintf(err, errlen, "DeviceInputWidth / DeviceInputHeight / DeviceInputChromaLeft describe a source the device scales: they need DeviceInputScale=1..3"); return -1; }
+    if (inp->device_input_yuv && !inp->device_input) { snprintf(err, errlen, "DeviceInputYUV=%d names the layout of a picture pushed from device memory: it needs DeviceInput=1", inp->device_input_yuv); return -1; }
+    if (inp->device_input_yuv && !jm_yuv_format_ok(inp->device_input_yuv)) { snprintf(err, errlen, "DeviceInputYUV=%d not supported (0: 4:2:0, 32 I422, 33 NV16, 34 YUYV, 35 UYVY, 36 I444, 37 VUYA8, 40 I210, 41 P210, 42 Y210, 43 I410, 44 Y410)", inp->device_input_yuv); return -1; }
+    if (inp->device_input_yuv && inp->device_input_format) { snprintf(err, errlen, "DeviceInputYUV=%d and DeviceInputFormat=%d both name the layout of InputFile: set one of them", inp->device_input_yuv, inp->device_input_format); return -1; }
+    if (inp->device_input_yuv && inp->device_input_tensor) { snprintf(err, errlen, "DeviceInputYUV=%d and DeviceInputTensor=%d both name the layout of InputFile: set one of them", inp->device_input_yuv, inp->device_input_tensor); return -1; }
+    if (inp->device_input_yuv && !device_input_yuv_fn) { snprintf(err, errlen, "DeviceInputYUV=%d reduces the source to 4:2:0 on the device: it needs the device backend (this build has no 4:2:2 / 4:4:4 device input: DeviceInputYUV=0)", inp->device_input_yuv); return -1; }
+    if (inp->device_input_yuv && inp->device_input_yuv < 40 && inp->bit_depth_luma != 8) { snprintf(err, errlen, "DeviceInputYUV=%d holds 8-bit samples: it needs SourceBitDepthLuma=8 (got %d)", inp->device_input_yuv, inp->bit_depth_luma); return -1; }
+    if ((inp->device_input_yuv == 40 || inp->device_input_yuv == 43) && inp->bit_depth_luma != 9 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputYUV=%d holds 9- or 10-bit samples in 16-bit words: it needs SourceBitDepthLuma=9 or 10 (got %d)", inp->device_input_yuv, inp->bit_depth_luma); return -1; }
+    if ((inp->device_input_yuv == 41 || inp->device_input_yuv == 42 || inp->device_input_yuv == 44) && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputYUV=%d holds 10-bit samples: it needs SourceBitDepthLuma=10 (got %d)", inp->device_input_yuv, inp->bit_depth_luma); return -1; }
+    if (inp->device_input_yuv && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputYUV=%d reads 4:2:2 or 4:4:4 frames from InputFile: the synthetic source is 4:2:0 (InputFile=%s)", inp->device_input_yuv, inp->infile); return -1; }
+    if (inp->device_input_yuv && !inp->device_writer_async) { snprintf(err, errlen, "DeviceInputYUV=%d leaves no 4:2:0 source on the host, so the distortion comes from the device's SSDs: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1)", inp->device_input_yuv); return -1; }
+    if (!inp->device_input_scale && (inp->device_input_width || inp->device_input_height || (inp->device_input_chroma_left && !jm_yuv_is444(inp->device_input_yuv)))) { snprintf(err, errlen, "DeviceInputWidth / DeviceInputHeight / DeviceInputChromaLeft describe a source the device scales: they need DeviceInputScale=1..3"); return -1; }
     if (inp->device_input_scale && !inp->device_input) { snprintf(err, errlen, "DeviceInputScale=%d scales a picture pushed from device memory: it needs DeviceInput=1", inp->device_input_scale); return -1; }
     if (inp->device_input_scale && !device_input_scale_fn) { snprintf(err, errlen, "DeviceInputScale=%d scales the source on the device: it needs the device backend (this build has no device scaler: DeviceInputScale=0)", inp->device_input_scale); return -1; }
     if (inp->device_input_scale && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputScale=%d reads frames of DeviceInputWidth x DeviceInputHeight from InputFile: the synthetic source has the coded size (InputFile=%s)", inp->device_input_scale, inp->infile); return -1; }

@@ -456,6 +456,16 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fprintf(stderr, "DeviceInputTensor=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n", tensor_kind);
         return JMH_E_UNSUPPORTED_CFG;
     }
+    const int yuv_format = inp->device_input_yuv ? inp->device_input_yuv | (inp->device_input_chroma_left && jm_yuv_is444(inp->device_input_yuv) ? JMH_PIX_CHROMA_LEFT : 0) : 0;
+    const jm_device_push_rgb_fn device_input_yuv_fn = yuv_format ? jm_device_input_yuv() : NULL;
+    if (yuv_format && (rgb_format || tensor_kind || !device_input_fn || !device_input_yuv_fn)) {
+        fprintf(stderr, "DeviceInputYUV=%d needs DeviceInput=1 on the device backend, DeviceInputFormat=0 and DeviceInputTensor=0 (backend '%s')\n", inp->device_input_yuv, be->name);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
+    if (yuv_format && !inp->device_writer_async) {
+        fprintf(stderr, "DeviceInputYUV=%d needs DeviceWriterAsync=1 (no 4:2:0 source on the host: the distortion is the device's)\n", inp->device_input_yuv);
+        return JMH_E_UNSUPPORTED_CFG;
+    }
     const int scale = inp->device_input_scale;
     const jm_device_scale_fn device_scale_fn = scale ? jm_device_input_scale() : NULL;
     if (scale && (!device_input_fn || !device_scale_fn || !inp->device_writer_async)) {
@@ -495,6 +505,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     int synthetic = !strncmp(inp->infile, "synthetic:", 10);
     if (synthetic && rgb_format) { fprintf(stderr, "DeviceInputFormat=%d reads RGB frames from InputFile: the synthetic source is YUV\n", inp->device_input_format); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic && tensor_kind) { fprintf(stderr, "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV\n", tensor_kind); return JMH_E_UNSUPPORTED_CFG; }
+    if (synthetic && yuv_format) { fprintf(stderr, "DeviceInputYUV=%d reads 4:2:2 or 4:4:4 frames from InputFile: the synthetic source is 4:2:0\n", inp->device_input_yuv); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic && scale) { fprintf(stderr, "DeviceInputScale=%d reads frames of DeviceInputWidth x DeviceInputHeight from InputFile: the synthetic source has the coded size\n", scale); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic) seed = strtoull(inp->infile + 10, NULL, 10);
     else if (!(fin = fopen(inp->infile, "rb"))) { fprintf(stderr, "Input file %s does not exist\n", inp->infile); return JMH_E_INVALID_ARG; }
@@ -548,9 +559,10 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     jm_pic rec;
     memset(&rec, 0, sizeof(rec));
     /* DeviceInputFormat: one frame as read, height rows of 4 * width bytes (free again when its upload returns);
-       DeviceInputTensor: one frame of its file, in the same buffer */
-    const int raw_source = rgb_format || tensor_kind;
-    const size_t rgb_bytes = tensor_kind ? jm_tensor_frame_bytes(tensor_kind, src_w, src_h) : (size_t)4 * src_w * src_h;
+       DeviceInputTensor: one frame of its file, in the same buffer; DeviceInputYUV: one frame of its layout, likewise */
+    const int raw_source = rgb_format || tensor_kind || yuv_format;
+    const size_t rgb_bytes = tensor_kind ? jm_tensor_frame_bytes(tensor_kind, src_w, src_h)
+                           : yuv_format ? jm_yuv_frame_bytes(inp->device_input_yuv, src_w, src_h) : (size_t)4 * src_w * src_h;
     uint8_t *rgb = raw_source ? (uint8_t *)malloc(rgb_bytes) : NULL;
     /* DeviceInputScale with a YUV file: one frame as read, at its own size (free again when its upload returns) */
     jm_pic big;
@@ -637,6 +649,9 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             fprintf(log, " (the source is an RGB tensor, %s: quantised and converted on the device with the BT.%s matrix at %s range; the stream does not signal either)\n",
                     tensor_kind == 1 ? "rgb24" : tensor_kind == 2 ? "gbrp" : tensor_kind == 3 ? "gbrp10le" : "gbrpf32le",
                     inp->device_input_matrix ? "709" : "601", inp->device_input_full ? "full" : "limited");
+        if (yuv_format)
+            fprintf(log, " (the source is %s, format %d: its chroma is reduced to 4:2:0 on the device%s)\n", jm_yuv_is444(inp->device_input_yuv) ? "4:4:4" : "4:2:2",
+                    inp->device_input_yuv, yuv_format & JMH_PIX_CHROMA_LEFT ? ", left-sited" : "");
         if (drec.fn)
             fprintf(log, " (ReconFile holds %s %s: the display-size picture converted on the device with the BT.%s matrix at %s range and downloaded)\n",
                     drec.tensor ? "an RGB tensor," : "RGB, format",
@@ -806,7 +821,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         int idx = inp->start_frame + f;
         double tr = now_ms();
         if (raw_source) {
-            if (fseek(fin, (long)rgb_bytes * idx, SEEK_SET) || fread(rgb, 1, rgb_bytes, fin) != rgb_bytes) { fprintf(stderr, "ReadOneFrame: cannot read RGB frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
+            if (fseek(fin, (long)rgb_bytes * idx, SEEK_SET) || fread(rgb, 1, rgb_bytes, fin) != rgb_bytes) { fprintf(stderr, "ReadOneFrame: cannot read %s frame %d\n", yuv_format ? "YUV" : "RGB", idx); st_ret = JMH_E_INVALID_ARG; break; }
         } else
         if (synthetic) jm_synth_frame(&p->cur, inp->width, inp->height, seed, idx);
         else if (jm_read_yuv_frame(fin, scale ? &big : &p->cur, src_w, src_h, idx)) { fprintf(stderr, "ReadOneFrame: cannot read frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
@@ -838,6 +853,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             if (nal && !(r = device_slice_heads(d, &sl))) r = device_nal_fn(be->ctx, d->n, d->nh);
             if (!r) r = tensor_kind ? device_input_tensor_fn(be->ctx, rgb, tensor_kind, tensor_flags, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
                   : rgb_format ? device_input_rgb_fn(be->ctx, rgb, rgb_format, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
+                  : yuv_format ? device_input_yuv_fn(be->ctx, rgb, yuv_format, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
                   : device_input_fn ? device_input_fn(be->ctx, scale ? &big : &p->cur, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
                                 : device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
         } else

@@ -108,6 +108,12 @@ typedef struct jm_input {
                                   Needs DeviceWriterAsync 1 (no source of the coded size on the host).  0: off */
     int  device_input_width, device_input_height;
     int  device_input_chroma_left;   /* (this build) DeviceInputChromaLeft 1: 4:2:0 chroma is left-sited (0: centred) */
+    int  device_input_yuv;     /* (this build) DeviceInputYUV 32..37, 40..44: with DeviceInput 1 InputFile holds 4:2:2 or
+                                  4:4:4 frames in that layout of include/jmhip_yuv.h, tightly packed (planes one
+                                  after the other), uploaded raw and reduced to 4:2:0 on the device; 0: 4:2:0.
+                                  Needs DeviceWriterAsync 1 and the matching SourceBitDepthLuma; excludes
+                                  DeviceInputFormat and DeviceInputTensor; combines with DeviceInputScale.  With a
+                                  4:4:4 layout DeviceInputChromaLeft 1 also sets JMH_PIX_CHROMA_LEFT            */
     int  device_recon_format;  /* (this build) DeviceReconFormat 16..19: ReconFile holds the display-size picture
                                   converted on the device to packed RGB (height rows of 4 * width bytes, the
                                   layouts of DeviceInputFormat; jmh_pull_picture of include/jmhip_output.h) and
@@ -308,6 +314,29 @@ typedef int (*jm_device_push_rgb_fn)(void *ctx, const void *rgb, int format, int
                                      const jmh_coded_slice *slices, int crop_w, int crop_h);
 void jm_set_device_input_rgb(jm_device_push_rgb_fn fn);
 jm_device_push_rgb_fn jm_device_input_rgb(void);
+/* DeviceInputYUV 32..37, 40..44: the backend's push of a 4:2:2 or 4:4:4 picture (jmh_frame_push_coded_device with a
+   format of include/jmhip_yuv.h, its flag included).  frame holds jm_yuv_frame_bytes(format, disp_w, disp_h) bytes
+   as read: the layout's planes one after the other, every row tight */
+void jm_set_device_input_yuv(jm_device_push_rgb_fn fn);
+jm_device_push_rgb_fn jm_device_input_yuv(void);
+/* the layouts of a DeviceInputYUV file: whether the key names one, whether it is 4:4:4, the bytes of a row of its
+   plane sp (0 for a plane the layout has not) and of a frame (every plane has h rows) */
+static inline int jm_yuv_format_ok(int f) { return (f >= 32 && f <= 37) || (f >= 40 && f <= 44); }
+static inline int jm_yuv_is444(int f) { return f == 36 || f == 37 || f == 43 || f == 44; }
+static inline size_t jm_yuv_row_bytes(int f, int sp, int w) {
+    const size_t es = f >= 40 ? 2 : 1;
+    switch (f) {
+    case 32: case 40: return (size_t)(sp == 0 ? w : w / 2) * es;      /* I422, I210: planar            */
+    case 33: case 41: return sp < 2 ? (size_t)w * es : 0;             /* NV16, P210: Y + interleaved UV */
+    case 34: case 35: case 42: return sp == 0 ? (size_t)2 * w * es : 0;   /* YUYV, UYVY, Y210          */
+    case 36: case 43: return (size_t)w * es;                          /* I444, I410: planar            */
+    case 37: case 44: return sp == 0 ? (size_t)4 * w : 0;             /* VUYA8, Y410: a dword a pixel  */
+    }
+    return 0;
+}
+static inline size_t jm_yuv_frame_bytes(int f, int w, int h) {
+    return (jm_yuv_row_bytes(f, 0, w) + jm_yuv_row_bytes(f, 1, w) + jm_yuv_row_bytes(f, 2, w)) * (size_t)h;
+}
 /* DeviceInputTensor 1..4: the backend's push of a frame as a device tensor (jmh_frame_push_coded_tensor).
    frame holds jm_tensor_frame_bytes(kind, disp_w, disp_h) bytes as read; flags: JMH_PIX_BT709 | JMH_PIX_FULL_RANGE */
 typedef int (*jm_device_push_tensor_fn)(void *ctx, const void *frame, int kind, int flags, int disp_w, int disp_h, const jmh_frame_params *fp,

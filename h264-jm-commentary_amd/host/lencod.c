@@ -103,6 +103,32 @@ static int gpu_push_device_rgb(void *ctx, const void *rgb, int format, int dw, i
     pic.stream = gpu_in.stream;
     return jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch);
 }
+/* DeviceInputYUV 32..37, 40..44: the 4:2:2 or 4:4:4 frame as read (its planes one after the other, rows tight),
+   through the same buffer and stream; the device reduces it to 4:2:0 */
+static int gpu_push_device_yuv(void *ctx, const void *frame, int format, int dw, int dh, const jmh_frame_params *fp, int n, const jmh_coded_slice *sl,
+                               int cw, int ch) {
+    const int layout = format & ~JMH_PIX_CHROMA_LEFT;
+    const size_t bytes = jm_yuv_frame_bytes(layout, dw, dh);
+    int r;
+    if (!gpu_in.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_in.stream))) return r;
+    if (gpu_in.bytes < bytes) {
+        if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_in.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_in.buf))) return r;
+        gpu_in.bytes = bytes;
+    }
+    if ((r = jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, frame, bytes, gpu_in.stream))) return r;
+    jmh_device_picture pic;
+    memset(&pic, 0, sizeof(pic));
+    pic.format = format;
+    pic.width = dw; pic.height = dh;
+    size_t off = 0;
+    for (int sp = 0; sp < 3 && jm_yuv_row_bytes(layout, sp, dw); sp++) {
+        pic.plane[sp] = (const uint8_t *)gpu_in.buf + off;
+        pic.stride[sp] = (int64_t)jm_yuv_row_bytes(layout, sp, dw);
+        off += jm_yuv_row_bytes(layout, sp, dw) * dh;
+    }
+    pic.stream = gpu_in.stream;
+    return jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch);
+}
 /* DeviceInputTensor 1..4: the frame as read (rgb24, gbrp, gbrp10le, gbrpf32le), through the same buffer and
    stream, described as a device tensor; the device quantises and converts it */
 static int gpu_push_device_tensor(void *ctx, const void *frame, int kind, int flags, int dw, int dh, const jmh_frame_params *fp, int n,
@@ -191,6 +217,7 @@ int main(int argc, char **argv) {
     jm_input_defaults(&inp);
     jm_set_device_input(gpu_push_device);   /* before PatchInp: it rejects DeviceInput on a backend without one */
     jm_set_device_input_rgb(gpu_push_device_rgb);
+    jm_set_device_input_yuv(gpu_push_device_yuv);
     jm_set_device_input_tensor(gpu_push_device_tensor);
     jm_set_device_input_scale(gpu_input_scale);
     jm_set_device_output(gpu_pull_recon);

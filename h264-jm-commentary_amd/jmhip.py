@@ -294,6 +294,14 @@ _SIGS_RGB = {
 }
 EXPORTED_RGB = list(_SIGS_RGB)
 
+# ---- 4:2:2 and 4:4:4 pictures pushed from the device (include/jmhip_yuv.h; additive to ABI 14, no entry point) ----
+JMH_PIX_I422, JMH_PIX_NV16, JMH_PIX_YUYV, JMH_PIX_UYVY, JMH_PIX_I444, JMH_PIX_VUYA8 = 32, 33, 34, 35, 36, 37
+JMH_PIX_I210, JMH_PIX_P210, JMH_PIX_Y210, JMH_PIX_I410, JMH_PIX_Y410 = 40, 41, 42, 43, 44
+JMH_PIX_CHROMA_LEFT = 1 << 10
+YUV_FORMATS = (JMH_PIX_I422, JMH_PIX_NV16, JMH_PIX_YUYV, JMH_PIX_UYVY, JMH_PIX_I444, JMH_PIX_VUYA8,
+               JMH_PIX_I210, JMH_PIX_P210, JMH_PIX_Y210, JMH_PIX_I410, JMH_PIX_Y410)
+YUV_444 = (JMH_PIX_I444, JMH_PIX_VUYA8, JMH_PIX_I410, JMH_PIX_Y410)
+
 # ---- RGB tensors pushed from the device (include/jmhip_tensor.h; additive to ABI 14) ----
 JMH_T_U8, JMH_T_U16, JMH_T_F16, JMH_T_BF16, JMH_T_F32 = 0, 1, 2, 3, 4
 TENSOR_ELEM_BYTES = {JMH_T_U8: 1, JMH_T_U16: 2, JMH_T_F16: 2, JMH_T_BF16: 2, JMH_T_F32: 4}
@@ -515,6 +523,83 @@ def to_device_rgb(array, format, pad_stride=0, misalign=0):
     rows = np.lib.stride_tricks.as_strided(buf[misalign:], (h, rb), (stride, 1))
     rows[:] = a.reshape(h, rb)
     return HostLayout(format, w, h, buf, [misalign], [stride])
+
+
+def to_device_yuv(planes, format, pad_stride=0, misalign=0):
+    """A 4:2:2 or 4:4:4 numpy picture planes = (y, u, v) laid out in the requested format of
+    include/jmhip_yuv.h (JMH_PIX_I422 .. JMH_PIX_Y410, JMH_PIX_CHROMA_LEFT allowed) as a HostLayout.
+    y is h x w; u and v are h x w/2 for the 4:2:2 formats and h x w for the 4:4:4 ones.  The packed
+    layouts are interleaved here.  pad_stride, misalign: as for to_device (the formats of 16-bit words
+    want them even, VUYA8 and Y410 multiples of 4; this function does not insist, so that a test can
+    build what the library must refuse).  P210 and Y210 get noise in the low 6 bits of every word,
+    VUYA8 and Y410 in their alpha."""
+    layout = format & ~JMH_PIX_CHROMA_LEFT
+    if layout not in YUV_FORMATS:
+        raise ValueError(f"to_device_yuv: format {format} is not one of include/jmhip_yuv.h")
+    dt = np.uint16 if layout >= JMH_PIX_I210 else np.uint8
+    y, u, v = (np.ascontiguousarray(a, dt) for a in planes)
+    h, w = y.shape
+    if u.shape != v.shape or u.shape != (h, w if layout in YUV_444 else w // 2):
+        raise ValueError("to_device_yuv: the chroma planes do not have the format's size")
+    noise = lambda a, m: (np.arange(a.size, dtype=np.uint32).reshape(a.shape) * 37 + 11) & m
+    if layout in (JMH_PIX_P210, JMH_PIX_Y210):
+        y, u, v = ((a.astype(np.uint32) << 6 | noise(a, 63)).astype(np.uint16) for a in (y, u, v))
+    if layout in (JMH_PIX_I422, JMH_PIX_I444, JMH_PIX_I210, JMH_PIX_I410):
+        src = [y, u, v]
+    elif layout in (JMH_PIX_NV16, JMH_PIX_P210):
+        uv = np.empty((h, w), dt)
+        uv[:, 0::2], uv[:, 1::2] = u, v
+        src = [y, uv]
+    elif layout in (JMH_PIX_YUYV, JMH_PIX_UYVY, JMH_PIX_Y210):
+        p = np.empty((h, 2 * w), dt)
+        o = 1 if layout == JMH_PIX_UYVY else 0                          # where Y0 lies in Y0 U Y1 V / U Y0 V Y1
+        p[:, o::4], p[:, o + 2::4] = y[:, 0::2], y[:, 1::2]
+        p[:, 1 - o::4], p[:, 3 - o::4] = u, v
+        src = [p]
+    elif layout == JMH_PIX_VUYA8:
+        p = np.empty((h, w, 4), np.uint8)
+        p[..., 0], p[..., 1], p[..., 2], p[..., 3] = v, u, y, noise(y, 255)
+        src = [p.reshape(h, 4 * w)]
+    else:                                                               # Y410
+        p = u.astype(np.uint32) | y.astype(np.uint32) << 10 | v.astype(np.uint32) << 20 | noise(y, 3) << 30
+        src = [p.astype("<u4")]
+    offsets, strides, end = [], [], 0
+    for a in src:
+        rb = a.shape[1] * a.itemsize
+        offsets.append((end + 255) // 256 * 256 + misalign)
+        strides.append(rb + pad_stride)
+        end = offsets[-1] + (a.shape[0] - 1) * strides[-1] + rb      # no byte behind the last row's samples
+    buf = np.full(end, 0xA5, np.uint8)
+    for a, o, st in zip(src, offsets, strides):
+        rb = a.shape[1] * a.itemsize
+        rows = np.lib.stride_tricks.as_strided(buf[o:], (a.shape[0], rb), (st, 1))
+        rows[:] = np.ascontiguousarray(a).view(np.uint8).reshape(a.shape[0], rb)
+    return HostLayout(format, w, h, buf, offsets, strides)
+
+
+def yuv_reduce(y, u, v, format, bit_depth):
+    """The numpy reference of include/jmhip_yuv.h: the planar 4:2:2 or 4:4:4 samples (as given to
+    to_device_yuv) reduced to the 4:2:0 picture (y, u, v) of the source size, in exact integers.
+    Samples of I210 / I410 above maxv are taken as maxv first; luma is copied; chroma is
+    (C[2j][i] + C[2j+1][i] + 1) >> 1 for 4:2:2, the rounded mean of the 2x2 block for 4:4:4, and with
+    JMH_PIX_CHROMA_LEFT h(r) = C[r][max(2i-1, 0)] + 2 C[r][2i] + C[r][2i+1], (h(2j) + h(2j+1) + 4) >> 3."""
+    layout = format & ~JMH_PIX_CHROMA_LEFT
+    if layout not in YUV_FORMATS:
+        raise ValueError(f"yuv_reduce: format {format} is not one of include/jmhip_yuv.h")
+    dt = np.uint16 if bit_depth > 8 else np.uint8
+    y, u, v = (np.asarray(a).astype(np.int64) for a in (y, u, v))
+    if layout in (JMH_PIX_I210, JMH_PIX_I410):
+        y, u, v = (np.minimum(a, (1 << bit_depth) - 1) for a in (y, u, v))
+
+    def chroma(c):
+        if layout not in YUV_444:
+            return (c[0::2] + c[1::2] + 1) >> 1
+        if not format & JMH_PIX_CHROMA_LEFT:
+            return (c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2] + 2) >> 2
+        left = np.concatenate([c[:, :1], c[:, 1:-1:2]], axis=1)         # C[r][max(2i - 1, 0)]
+        hs = left + 2 * c[:, 0::2] + c[:, 1::2]
+        return (hs[0::2] + hs[1::2] + 4) >> 3
+    return y.astype(dt), chroma(u).astype(dt), chroma(v).astype(dt)
 
 
 class DeviceTensor:
@@ -1046,7 +1131,7 @@ class Encoder:
         _check(self.lib.jmh_device_upload(self.ctx, _addr(dst), _ptr(data), data.nbytes, stream), "jmh_device_upload")
 
     def device_picture(self, layout, stream=None, base=None):
-        """A HostLayout (to_device, to_device_rgb) uploaded: into base, or into a new allocation of exactly its
+        """A HostLayout (to_device, to_device_rgb, to_device_yuv) uploaded: into base, or into a new allocation of exactly its
         bytes (the caller frees .base).  Returns the DevicePicture."""
         if base is None:
             base = self.device_alloc(layout.buf.nbytes)

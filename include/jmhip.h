@@ -38,7 +38,8 @@
  * Coded pictures (a pipelined picture whose slice data is written behind its last macroblock and
  * whose pop returns the slice bytes and the distortion only): include/jmhip_coded.h, included
  * last, additive as well.  Pictures that are already on the device (planar, NV12, P010; padded to
- * the coded size by the library): include/jmhip_input.h, additive as well.  NAL units finished on
+ * the coded size by the library): include/jmhip_input.h, additive as well; its 4:2:2 and 4:4:4
+ * formats, reduced to 4:2:0 by the library: include/jmhip_yuv.h (values only).  NAL units finished on
  * the device, so that a coded picture's pop returns its Annex B access unit: include/jmhip_nal.h,
  * additive as well.
  *
@@ -386,6 +387,7 @@ int  jmh_read_qpel(jmh_ctx *ctx, uint8_t *out);
 #include "jmhip_input.h"
 #include "jmhip_nal.h"
 #include "jmhip_rgb.h"
+#include "jmhip_yuv.h"
 #include "jmhip_tensor.h"
 #include "jmhip_spiral.h"
 #include "jmhip_scale.h"
