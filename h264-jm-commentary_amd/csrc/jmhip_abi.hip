@@ -12,24 +12,11 @@
 // Per-picture device state lives in a ring of nring = depth + 2 entries (source, recon,
 // deblocked recon, MV / ref_idx / ipred maps, results, MbScratch); an entry is reused only once
 // no picture in flight reads or writes it and its results were popped.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <deque>
-#include <vector>
+//
+// The context itself is in jmh_ctx.h; device memory handed in or out by the caller (device sources, the scaler,
+// pulls) is jmhip_io.hip's.
 #include <algorithm>
-#include "jmh_launch.h"
-#include "jmh_cavlc.h"
-#include "jmh_cabac.h"
-#include "jmh_cabac_rate.h"
-#include "jmh_ingest.h"
-#include "jmh_scale.h"
-#include "jmh_rgb.h"
-#include "jmh_yuv.h"
-#include "jmh_tensor.h"
-#include "jmh_output.h"
-#include "jmh_nal.h"
+#include "jmh_ctx.h"
 #include "jmh_spiral.h"
 
 // Coded pictures: bytes of output per macroblock that a picture's writer is queued with, unless
@@ -50,12 +37,7 @@ static int q_selector(const jmh_config &cfg, bool i_slice) {
 // JMH_FLAG_KERNEL_TIMING brackets every KT_STRIDE-th tick's two launches with events: the
 // averages are sampled uniformly while the event packets stay off most launches
 #define KT_STRIDE 32                      // an event pair between two launches costs ~7 us on that tick
-// ring of begin/end event pairs; completed pairs are folded into `sum` (ms)
-struct EvRing {
-    std::vector<hipEvent_t> a, b;
-    int cap = 0, head = 0, count = 0, n = 0;
-    float sum = 0;
-};
+// (EvRing, jmh_ctx.h: a ring of begin/end event pairs)
 static int ring_init(EvRing &r, int cap) {
     r.cap = cap; r.head = r.count = r.n = 0; r.sum = 0;
     r.a.assign(cap, nullptr); r.b.assign(cap, nullptr);
@@ -95,241 +77,7 @@ static void ring_drain(EvRing &r, float &sum, int &n) {
     r.sum = 0; r.n = 0;
 }
 
-
-// NAL units finished on the device (jmhip_nal.h): the buffers of one access unit, a
-// ring entry's or the synchronous seam's
-struct NalBuf {
-    uint8_t *h, *d;                      // pinned / device: heads, where, chunk starts, chunk records, unit places, meta (NalLayout)
-    int ucap, maxch;                     //   the units and chunks they hold
-    uint8_t *out;                        // device: the access unit
-    size_t out_cap;
-};
-// offsets into NalBuf::h / d (each a multiple of 8)
-struct NalLayout {
-    size_t heads, where, cs, ch, uout, meta, bytes;
-    NalLayout(int ucap, int maxch) {
-        auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-        heads = 0;
-        where = up8((size_t)ucap * sizeof(jmh_nal_head));
-        cs = where + (size_t)ucap * 3 * sizeof(int64_t);
-        ch = up8(cs + ((size_t)ucap + 1) * sizeof(int32_t));
-        uout = ch + (size_t)maxch * sizeof(jmn_chunk);
-        meta = uout + (size_t)ucap * 2 * sizeof(int64_t);
-        bytes = meta + JMN_META_WORDS * sizeof(uint64_t);
-    }
-};
-static_assert(sizeof(jmn_chunk) % 8 == 0 && sizeof(jmh_nal_range) == 2 * sizeof(int64_t), "NalLayout");
-
-// one ring entry: everything one picture in flight owns
-struct PicBuf {
-    uint8_t *src, *rec, *dbk;            // device: source (jmh_frame_push), recon, deblocked recon
-    int16_t *mv;
-    int8_t *refidx, *ipred;
-    jmh_mb_result *res;
-    MbScratch *scr;
-    jmh_mb_result *h_res;                // pinned host copies (allocated on first readback use)
-    uint8_t *h_src, *h_rec, *h_dbk;
-    hipEvent_t ev_src, ev_t0, ev_done;   // staging reuse / push..done timing
-    hipEvent_t ev_fin;                   // the picture's last tick (the copy stream's readback waits)
-    uint8_t *cab;                        // RDOptimization 1: the slices' context states,
-    uint32_t *range;                     //   codIRange, the MBs' context-selection records
-    jmr_mbinfo *mbi;
-    RdoPic *h_rp;                        //   pinned staging of the entry's RdoPic (after scr)
-    hipEvent_t ev_rp;                    //   its H2D copy (h_rp is rewritten only after it completes)
-    int recon_read;                      // h_rec holds the occupant's reconstruction
-    int unpopped;                        // readback picture not yet popped
-    int deblocked;                       // the occupant was deblocked on the device (dbk valid)
-    uint32_t gen;                        // dataflow: occupants so far (the flag value of its MBs)
-    // coded pictures (jmhip_coded.h): the entry's own writer buffers, on its first coded picture
-    int coded;                           // the occupant is a coded picture: no readback, its writer queued behind it
-    int cd_n, cd_cw, cd_ch;              //   its slices, its crop
-    uint8_t *cd_h, *cd_d;                // pinned / device: descriptors [nmb], where [nmb], meta (CodedLayout)
-    jmh_coded_slice *cd_sl;              // pinned (inside cd_h): the caller's descriptors, for the synchronous fallback
-    uint8_t *cd_out;                     // device: the picture's output region
-    size_t cd_cap;                       //   its bytes
-    int nal_armed;                       // the occupant was armed (jmh_coded_nal_heads): its pop returns the access unit
-    NalBuf nal;                          //   the entry's NAL buffers, on its first armed picture
-    // device pictures (jmhip_input.h)
-    int dev_fmt;                         // the occupant was pushed as a device picture: its format + 1, else 0 (a host picture, a tensor)
-    hipEvent_t ev_in;                    //   the caller's stream at the push (created on first use)
-    // pulled pictures (jmhip_output.h)
-    hipEvent_t ev_out;                   // the last pull that read rec / dbk (created on first use); the next claim waits for it
-};
-
-// offsets into PicBuf::cd_h / cd_d (each a multiple of 8)
-struct CodedLayout {
-    size_t sl, where, meta, user, bytes;
-    explicit CodedLayout(size_t nmb) {
-        sl = 0;
-        where = sl + nmb * 24;           // jmh_slice_desc is 20 bytes, jmh_cabac_slice_desc 16
-        meta = where + nmb * sizeof(jmh_slice_bytes);
-        user = meta + JMH_WRITER_META_BYTES;
-        bytes = user + nmb * sizeof(jmh_coded_slice);   // (host only)
-    }
-};
-static_assert(sizeof(jmh_slice_bytes) == sizeof(jmh_cabac_slice_bytes) && sizeof(jmh_slice_desc) <= 24 && sizeof(jmh_cabac_slice_desc) <= 24,
-              "CodedLayout");
-
-// a picture in flight (not yet fully issued)
-struct Flight {
-    int id, entry, ref_entry;            // ref_entry: ring entry read as reference (-1: d_ref / none)
-    int tmv_entry;                       // ring entry whose motion field EPZS reads (-1: none)
-    int pred_id;                         // picture it must trail by PIPE_LAG diagonals (-1: none)
-    int stage, started, readback;
-    PicParams pp;
-};
-
 enum { REF_NONE, REF_BUF, REF_REC, REF_DBK };
-
-static_assert(JMS_INVALID == JMH_E_INVALID_ARG && JMS_UNSUPPORTED == JMH_E_UNSUPPORTED_CFG && JMS_TAPS_MAX == JMH_SCALE_TAPS_MAX &&
-              JMS_SRC_MAX == JMH_SCALE_SRC_MAX && JMS_LANCZOS3 == JMH_SCALE_LANCZOS3 && JMS_CHROMA_LEFT == JMH_SCALE_CHROMA_LEFT, "jmh_scale.h restates jmhip_scale.h");
-static_assert(JMY_I422 == JMH_PIX_I422 && JMY_NV16 == JMH_PIX_NV16 && JMY_YUYV == JMH_PIX_YUYV && JMY_UYVY == JMH_PIX_UYVY && JMY_I444 == JMH_PIX_I444 &&
-              JMY_VUYA8 == JMH_PIX_VUYA8 && JMY_I210 == JMH_PIX_I210 && JMY_P210 == JMH_PIX_P210 && JMY_Y210 == JMH_PIX_Y210 && JMY_I410 == JMH_PIX_I410 &&
-              JMY_Y410 == JMH_PIX_Y410 && JMY_CHROMA_LEFT == JMH_PIX_CHROMA_LEFT, "jmh_yuv.h restates jmhip_yuv.h");
-// the tables of one geometry of the scaler (jmh_scale.h, jms_pack_axis) on the device; h: what was uploaded, kept
-// while the copy may be pending (up)
-#define SCALE_TABS 8
-struct ScaleTab {
-    int key[6];                          // source w, h, output w, h, filter, flags
-    uint8_t *d = nullptr;
-    std::vector<uint8_t> h;
-    hipEvent_t up = nullptr;
-    size_t off[2][4];                    // [luma, chroma][fh, fv, th, tv]: bytes into d
-    int T[2][2];                         // [luma, chroma][horizontal, vertical]
-    uint64_t used = 0;
-};
-
-struct jmh_ctx {
-    jmh_config cfg;
-    int dev;
-    hipStream_t st;                      // the wavefront ticks (and source uploads)
-    hipStream_t cst;                     // readback of finished pictures, overlapping later ticks
-    hipStream_t sst = nullptr;           // RDO on: k_rdo_intra beside k_rdo_inter
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int W, H, Wc, Hc, mbw, mbh, sr, side, npos, qstride, qplane, nd;
-    size_t fsize, n4, nmb;               // bytes of one 4:2:0 picture (Y then U then V)
-    uint8_t *d_ref, *d_qpel, *d_slots;   // explicit reference (set_reference), a1 seam, slots
-    struct { void *cur, *ref; } spic[2]; // luma pictures of the per-block searches, by sample width: [0] 8-bit
-                                         //   (jmh_search_pictures), [1] 16-bit, the High 10 seams (..._u16)
-    uint32_t *d_ordtab;                  // FFS order keys of the analysis threads' strips (ordtab_fill)
-    int bd, ps, maxv;                    // picture bit depth, bytes per sample (1, 2), (1 << bd) - 1
-    int hbd_bits;                        // bit depth of the 16-bit search pictures
-    int nslots;
-    int depth, nring;
-    std::vector<PicBuf> ring;
-    std::deque<Flight> fl;               // issued-incompletely pictures, oldest first
-    std::deque<int> popq;                // readback pictures (ring entries) not yet popped
-    int next_id, next_entry;
-    int last_id, last_entry;             // the last pushed picture
-    int ref_kind, ref_entry;             // the reference of the next pushed picture
-    int cur_entry;                       // results visible through get_mb_result / read_*
-    unsigned long long *d_prof;          // JMH_PHASE_PROF=<mb>: per-phase wall clock of one MB
-    int prof_mb;
-    unsigned long long *d_bprof;         // JMH_BLOCK_PROF=<tick>: k_mb_analyse block start/end/role
-    int bprof_tick, bprof_blocks;
-    uint8_t *h_stage_ref;
-    EvRing ring_interp, ring_mb, ring_an, ring_fin;   // ring_an / ring_fin: JMH_FLAG_KERNEL_TIMING
-    jmh_timing timing;
-    int ticks_total;
-    std::vector<int> dcount, dymin;
-    int lag;                             // stages a picture trails its reference picture by
-    // RDOptimization 1: the RD stage schedule (MB addresses in stage order, offsets per stage),
-    // the tick's candidate scratch, slices per picture
-    int32_t *d_sched, *d_soff;
-    void *d_rscr;
-    void *d_ffs;                         // RDO + SearchMode 0: the tick MBs' SAD tables (k_rdo_inter)
-    int nslice;
-    // dataflow wavefront (k_mb_flow): ticks are not launched one by one but
-    // collected into a segment of macroblocks in tick order, launched as one grid on a flush
-    bool flow = false;
-    int seg_max = 0;                     // ticks per segment before a flush (JMH_FLOW_SEG)
-    int seg_min = 8;                     // ... or, once the device is idle, this many (2 / 4 / 16 within
-                                         //   noise: profiles/r10h_flow_bench20_ab.txt)
-    hipEvent_t ev_flow = nullptr;        // the last segment launch's end: a segment of >= seg_min ticks
-                                         //   is flushed as soon as the device has run out of work
-    std::vector<FlowPic> fpic;           // per ring entry: parameters + flag generations
-    std::vector<uint32_t> seg;           // the pending segment's macroblocks (FLOW_ITEM)
-    unsigned long long seg_mask = 0;     // ring entries the pending segment reads or writes
-    int seg_ticks = 0;
-    size_t seg_cap = 0;                  // items the device / staging buffers hold
-    // segment buffers, alternating: pinned staging -> device on the upload stream, beside the
-    // previous segment's launch (a buffer is rewritten once the launch that read it has ended)
-    uint8_t *d_seg[2] = {nullptr, nullptr};   // device: FlowPic[nring], then the items
-    uint8_t *h_seg[2] = {nullptr, nullptr};   // pinned staging
-    hipEvent_t ev_seg[2] = {nullptr, nullptr};   // the upload out of h_seg[i] / into d_seg[i] done
-    hipEvent_t ev_kseg[2] = {nullptr, nullptr};  // the launch that read d_seg[i] done
-    hipStream_t ust = nullptr;           // the segment uploads
-    int seg_slot = 0;
-    uint32_t *d_flags = nullptr;         // [nring][nmb] generations of the finished MBs
-    unsigned *d_head = nullptr;          // ticket counter
-    unsigned head_base = 0;
-    unsigned *h_err = nullptr;           // pinned, device-written: a dependency wait timed out
-    int fprof_launch = -1, flow_count = 0;   // debug: JMH_FLOW_PROF=<launch> -> JMH_FLOW_PROF_OUT (raw u64)
-    unsigned long long *d_fprof = nullptr;
-    size_t fprof_n = 0;
-    std::vector<uint32_t> fprof_items;
-    jmh_cavlc_state *cavlc = nullptr;    // device CAVLC writer (jmh_cavlc.hip): its own stream, created on first use
-    int cabac_split = 0;                 // jmh_cabac_set_split: bins per chunk of the split coder, 0 off
-    jmh_cabac_state *cabac = nullptr;    // device CABAC writer (jmh_cabac.hip): the same
-    size_t coded_cap = 0;                // coded pictures: bytes of output per macroblock queued with a picture
-    std::vector<void *> coded_retired;   //   outgrown output regions: freed with the context
-    uint8_t *h_coded_pic = nullptr;      //   pinned: jmh_read_recon / jmh_read_deblocked of a coded picture
-    bool nal_armed = false;              // jmh_coded_nal_heads: the next coded push takes nal_arm
-    std::vector<jmh_nal_head> nal_arm;
-    NalBuf nalw = {};                    // jmh_nal_wrap: its buffers,
-    uint8_t *nalw_pay = nullptr;         //   the payload on the device
-    size_t nalw_pay_cap = 0;
-    // device pictures: the I010 clamp counts, a word per ring entry and one for the unit seam (on the
-    // first I010 picture), the count of the picture last popped, the last device push
-    unsigned long long *d_clamp = nullptr, *h_clamp = nullptr;
-    uint64_t last_clamped = 0;
-    int last_dev_entry = -1;
-    uint8_t *up_h = nullptr;             // jmh_device_upload on a stream: its pinned buffer,
-    size_t up_cap = 0;
-    hipEvent_t ev_up = nullptr;          //   the last copy out of it
-    hipStream_t ost = nullptr;           // pulls without a caller's stream, the convert seams, downloads (created on first use)
-    // jmh_input_scale (jmhip_scale.h): the setting (filter 0: off), the tables of the geometries last used and the
-    // scratch picture the ingest kernels pack into.  All of it is allocated, written, read and released on st
-    jmh_scale scale = {0, 0, 0, 0};
-    std::vector<ScaleTab> scale_tabs;
-    uint64_t scale_tick = 0;
-    uint8_t *d_scl = nullptr;
-    size_t scl_cap = 0;
-};
-
-#define HCHK(x)                                                                  \
-    do {                                                                         \
-        hipError_t e_ = (x);                                                     \
-        if (e_ != hipSuccess) {                                                  \
-            fprintf(stderr, "jmhip: %s failed: %s\n", #x, hipGetErrorString(e_)); \
-            return JMH_E_HIP;                                                    \
-        }                                                                        \
-    } while (0)
-
-extern "C" {
-
-int jmh_abi_version(void) { return JMH_ABI_VERSION; }
-
-const char *jmh_strerror(int s) {
-    switch (s) {
-    case JMH_OK: return "ok";
-    case JMH_E_INVALID_ARG: return "invalid argument";
-    case JMH_E_HIP: return "HIP runtime error";
-    case JMH_E_OOM: return "out of memory";
-    case JMH_E_UNSUPPORTED_CFG: return "unsupported configuration";
-    case JMH_E_STATE: return "invalid call order";
-    case JMH_E_NO_DEVICE: return "no HIP device";
-    }
-    return "unknown status";
-}
-
-int jmh_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-}  // extern "C"
 
 static void free_entry(PicBuf &b) {
     void *dev_bufs[] = {b.src, b.rec, b.dbk, b.mv, b.refidx, b.ipred, b.res, b.scr, b.cab, b.range, b.mbi, b.cd_d, b.cd_out, b.nal.d, b.nal.out};
@@ -381,19 +129,6 @@ static int alloc_host(jmh_ctx *c, PicBuf &b, bool with_src) {
         }
     return JMH_OK;
 }
-
-// device temporaries of the unit seams: freed on every return path
-struct DevTemps {
-    std::vector<void *> p;
-    ~DevTemps() { for (void *q : p) if (q) (void)hipFree(q); }
-    template <class T> hipError_t alloc(T **out, size_t n) {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, n);
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T *)q;
-        return e;
-    }
-};
 
 static void ordtab_fill(std::vector<uint32_t> &tab, int sr);
 
@@ -448,13 +183,35 @@ static int rdo_schedule(jmh_ctx *c, std::vector<int> &order, std::vector<int> &o
 }
 
 // the host waits for every pull queued so far (jmh_device_output_wait)
-static int output_wait(jmh_ctx *c) {
+int output_wait(jmh_ctx *c) {
     for (PicBuf &b : c->ring)
         if (b.ev_out) HCHK(hipEventSynchronize(b.ev_out));
     return JMH_OK;
 }
 
+// ---- the library and the context's life ----
 extern "C" {
+
+int jmh_abi_version(void) { return JMH_ABI_VERSION; }
+
+const char *jmh_strerror(int s) {
+    switch (s) {
+    case JMH_OK: return "ok";
+    case JMH_E_INVALID_ARG: return "invalid argument";
+    case JMH_E_HIP: return "HIP runtime error";
+    case JMH_E_OOM: return "out of memory";
+    case JMH_E_UNSUPPORTED_CFG: return "unsupported configuration";
+    case JMH_E_STATE: return "invalid call order";
+    case JMH_E_NO_DEVICE: return "no HIP device";
+    }
+    return "unknown status";
+}
+
+int jmh_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
 
 void jmh_destroy(jmh_ctx *c) {
     if (!c) return;
@@ -711,8 +468,7 @@ static inline uint16_t pack_row16(uint16_t *d, const uint16_t *s, int n) {
     for (int x = 0; x < n; x++) { d[x] = s[x]; acc |= s[x]; }
     return acc;
 }
-static bool pack_planes(uint8_t *dst, int W, int H, const void *yv, const void *uv, const void *vv, int sy, int sc, int ps,
-                        int maxv) {
+bool pack_planes(uint8_t *dst, int W, int H, const void *yv, const void *uv, const void *vv, int sy, int sc, int ps, int maxv) {
     const uint8_t *y = (const uint8_t *)yv, *u = (const uint8_t *)uv, *v = (const uint8_t *)vv;
     uint8_t *du = dst + (size_t)W * H * ps, *dv = du + (size_t)W * H / 4 * ps;
     if (ps == 1) {
@@ -733,7 +489,7 @@ static bool pack_planes(uint8_t *dst, int W, int H, const void *yv, const void *
     return (acc & ~maxv) == 0;   // maxv = 2^bd - 1: every sample <= maxv iff no bit above it is set
 }
 
-static void unpack_planes(const uint8_t *src, int W, int H, void *yv, void *uv, void *vv, int sy, int sc, int ps) {
+void unpack_planes(const uint8_t *src, int W, int H, void *yv, void *uv, void *vv, int sy, int sc, int ps) {
     uint8_t *y = (uint8_t *)yv, *u = (uint8_t *)uv, *v = (uint8_t *)vv;
     size_t ls = (size_t)W * H * ps;
     for (int r = 0; r < H; r++) memcpy(y + (size_t)r * sy * ps, src + (size_t)r * W * ps, (size_t)W * ps);
@@ -1206,31 +962,6 @@ static int set_reference_any(jmh_ctx *c, int list, int ref_idx, const void *y, c
     c->ref_kind = REF_BUF; c->ref_entry = -1;
     return JMH_OK;
 }
-extern "C" {
-int jmh_set_reference(jmh_ctx *c, int list, int ref_idx, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc) {
-    return set_reference_any(c, list, ref_idx, y, u, v, sy, sc, false);
-}
-int jmh_set_reference_u16(jmh_ctx *c, int list, int ref_idx, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc) {
-    return set_reference_any(c, list, ref_idx, y, u, v, sy, sc, true);
-}
-
-int jmh_set_reference_slot(jmh_ctx *c, int slot) {
-    if (!c || slot < -2 || slot >= c->nslots) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    if (slot < 0) {   // the last pushed picture (its recon, or its device deblocking): no copy
-        if (c->last_id < 0 || (slot == -2 && !c->ring[c->last_entry].deblocked)) return JMH_E_STATE;
-        c->ref_kind = slot == -1 ? REF_REC : REF_DBK;
-        c->ref_entry = c->last_entry;
-        return JMH_OK;
-    }
-    int r = drain(c);
-    if (r) return r;
-    HCHK(hipMemcpyAsync(c->d_ref, c->d_slots + (size_t)slot * c->fsize, c->fsize, hipMemcpyDeviceToDevice, c->st));
-    c->ref_kind = REF_BUF; c->ref_entry = -1;
-    return JMH_OK;
-}
-
-}  // extern "C"
 // a coded push: the caller's slices and crop (null: an ordinary picture)
 struct CodedPush { int n; const jmh_coded_slice *sl; int cw, ch; };
 
@@ -1268,198 +999,20 @@ static int alloc_coded(jmh_ctx *c, PicBuf &b) {
     return JMH_OK;
 }
 
-// the source of a pushed picture: host planes (strides in samples), a device picture or a device tensor
-struct PushSrc { const void *y, *u, *v; int sy, sc; bool wide; const jmh_device_picture *dev; const jmh_device_tensor *ten; };
-
-// the argument rules of jmhip_input.h (formats 0..3, no flag), of jmhip_rgb.h (16..19 with their flags) and of
-// jmhip_yuv.h (32..37 and 40..44 with their flag)
-static int check_device_pic(const jmh_ctx *c, const jmh_device_picture *p) {
-    if (!p) return JMH_E_INVALID_ARG;
-    const bool sc = c->scale.filter != JMH_SCALE_OFF;   // the source bound is the scaler's, not the coded size
-    const int BW = sc ? JMS_SRC_MAX : c->W, BH = sc ? JMS_SRC_MAX : c->H;
-    if (jmr_is_rgb(p->format)   ? jmr_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)
-        : jmy_is_yuv(p->format) ? jmy_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)
-                                : jmi_check(p->format, p->width, p->height, BW, BH, p->plane, p->stride)) return JMH_E_INVALID_ARG;
-    return sc ? jms_check(p->width, p->height, c->scale.out_width, c->scale.out_height, c->scale.filter) : JMH_OK;
-}
-// whether a context of this bit depth takes the (checked) format
-static bool device_depth_ok(const jmh_ctx *c, int format) {
-    return jmr_is_rgb(format) ? jmr_depth_ok(format, c->bd) : jmy_is_yuv(format) ? jmy_depth_ok(format, c->bd) : jmi_depth_ok(format, c->bd);
-}
-// whether the packing kernel of the (checked) format counts samples above maxv (jmh_device_input_clamped)
-static bool device_format_counts(int format) { return format == JMH_PIX_I010 || (jmy_is_yuv(format) && jmy_clamps(jmy_layout(format))); }
-
-// the argument rules of jmhip_tensor.h
-static int check_device_tensor(const jmh_ctx *c, const jmh_device_tensor *t) {
-    const bool sc = c->scale.filter != JMH_SCALE_OFF;
-    const int BW = sc ? JMS_SRC_MAX : c->W, BH = sc ? JMS_SRC_MAX : c->H;
-    if (!t || jmt_check(t->dtype, t->flags, t->width, t->height, BW, BH, t->chan, t->stride_x, t->stride_y)) return JMH_E_INVALID_ARG;
-    return sc ? jms_check(t->width, t->height, c->scale.out_width, c->scale.out_height, c->scale.filter) : JMH_OK;
-}
-
-// The tables of a w x h source under the current setting: the cached ones, or built and uploaded on st.  The entry
-// given up for them is the one used longest ago: its device memory is released in stream order behind its last
-// reader, its host copy after the upload out of it
-static int scale_tables(jmh_ctx *c, int w, int h, ScaleTab **out) {
-    const jmh_scale &s = c->scale;
-    const int key[6] = {w, h, s.out_width, s.out_height, s.filter, s.flags};
-    c->scale_tick++;
-    ScaleTab *slot = nullptr;
-    for (ScaleTab &t : c->scale_tabs)
-        if (t.d && !memcmp(t.key, key, sizeof key)) { t.used = c->scale_tick; *out = &t; return JMH_OK; }
-    if ((int)c->scale_tabs.size() < SCALE_TABS) {
-        c->scale_tabs.reserve(SCALE_TABS);               // entries are referred to by address
-        c->scale_tabs.emplace_back();
-        slot = &c->scale_tabs.back();
-    } else {
-        for (ScaleTab &t : c->scale_tabs) if (!slot || t.used < slot->used) slot = &t;
-        if (slot->up) HCHK(hipEventSynchronize(slot->up));
-        if (slot->d) HCHK(hipFreeAsync(slot->d, c->st));
-        slot->d = nullptr;
-    }
-    if (!slot->up && hipEventCreateWithFlags(&slot->up, hipEventDisableTiming) != hipSuccess) { slot->up = nullptr; return JMH_E_HIP; }
-    size_t end = 0;
-    std::vector<int32_t> first[2][2];
-    std::vector<int16_t> taps[2][2];
-    for (int pc = 0; pc < 2; pc++) {
-        const int ns[2] = {pc ? w / 2 : w, pc ? h / 2 : h}, nd[2] = {pc ? s.out_width / 2 : s.out_width, pc ? s.out_height / 2 : s.out_height};
-        for (int ax = 0; ax < 2; ax++) {
-            first[pc][ax].resize(nd[ax]);
-            taps[pc][ax].resize((size_t)nd[ax] * JMS_TAPS_MAX);
-            const int r = jms_taps(ns[ax], nd[ax], s.filter, pc && !ax && (s.flags & JMH_SCALE_CHROMA_LEFT), first[pc][ax].data(), taps[pc][ax].data(),
-                                   &slot->T[pc][ax]);
-            if (r) return r;
-        }
-        // the intermediate rows of k_scale's tallest tile fit its LDS (they do for every T <= JMS_TAPS_MAX)
-        if (jms_span(first[pc][1].data(), nd[1], slot->T[pc][1], pc ? c->H / 2 : c->H) > JMS_SPAN_MAX) return JMH_E_UNSUPPORTED_CFG;
-        const size_t bytes[4] = {(size_t)nd[0] * 4, (size_t)nd[1] * 4, (size_t)nd[0] * JMS_HPAIRS * 4, (size_t)nd[1] * JMS_VPAIRS * 4};
-        for (int i = 0; i < 4; i++) { slot->off[pc][i] = end; end += (bytes[i] + 15) & ~(size_t)15; }
-    }
-    slot->h.assign(end, 0);
-    for (int pc = 0; pc < 2; pc++) {
-        memcpy(slot->h.data() + slot->off[pc][0], first[pc][0].data(), first[pc][0].size() * 4);
-        memcpy(slot->h.data() + slot->off[pc][1], first[pc][1].data(), first[pc][1].size() * 4);
-        jms_pack_axis(first[pc][0].data(), taps[pc][0].data(), (int)first[pc][0].size(), slot->T[pc][0], 0, (uint32_t *)(slot->h.data() + slot->off[pc][2]));
-        jms_pack_axis(first[pc][1].data(), taps[pc][1].data(), (int)first[pc][1].size(), slot->T[pc][1], 1, (uint32_t *)(slot->h.data() + slot->off[pc][3]));
-    }
-    if (hipMallocAsync((void **)&slot->d, end, c->st) != hipSuccess) { slot->d = nullptr; return JMH_E_OOM; }
-    HCHK(hipMemcpyAsync(slot->d, slot->h.data(), end, hipMemcpyHostToDevice, c->st));
-    HCHK(hipEventRecord(slot->up, c->st));
-    memcpy(slot->key, key, sizeof key);
-    slot->used = c->scale_tick;
-    *out = slot;
-    return JMH_OK;
-}
-
-// With a scale set an ingest kernel packs its w x h source at its own size, rounded up to macroblocks, into the
-// context's scratch picture (scale_begin: where, and its size), and k_scale resamples that into dst (scale_end).
-// The scratch picture grows by a release and an allocation in stream order: behind its last reader
-static int scale_begin(jmh_ctx *c, int w, int h, uint8_t **out, int *W, int *H, ScaleTab **tab) {
-    int r = scale_tables(c, w, h, tab);
-    if (r) return r;
-    const int sW = (w + 15) & ~15, sH = (h + 15) & ~15;
-    const size_t need = (size_t)sW * sH * 3 / 2 * c->ps;
-    if (need > c->scl_cap) {
-        if (c->d_scl) HCHK(hipFreeAsync(c->d_scl, c->st));
-        c->d_scl = nullptr; c->scl_cap = 0;
-        if (hipMallocAsync((void **)&c->d_scl, need, c->st) != hipSuccess) { c->d_scl = nullptr; return JMH_E_OOM; }
-        c->scl_cap = need;
-    }
-    *out = c->d_scl; *W = sW; *H = sH;
-    return JMH_OK;
-}
-static int scale_end(jmh_ctx *c, const ScaleTab *t, int w, int h, int sW, int sH, uint8_t *dst) {
-    ScaleArgs a;
-    a.src = c->d_scl; a.dst = dst;
-    a.w = w; a.h = h; a.sW = sW; a.sH = sH; a.ow = t->key[2]; a.oh = t->key[3]; a.W = c->W; a.H = c->H;
-    for (int pc = 0; pc < 2; pc++) {
-        a.fh[pc] = (const int32_t *)(t->d + t->off[pc][0]); a.fv[pc] = (const int32_t *)(t->d + t->off[pc][1]);
-        a.th[pc] = (const uint32_t *)(t->d + t->off[pc][2]); a.tv[pc] = (const uint32_t *)(t->d + t->off[pc][3]);
-        a.nph[pc] = t->T[pc][0] / 2; a.npv[pc] = t->T[pc][1] / 2 + 1; a.tv_taps[pc] = t->T[pc][1];
-    }
-    a.maxv = c->maxv; a.P = 14 - c->bd;
-    HCHK(jmh_launch_scale(a, c->st));
-    return JMH_OK;
-}
-
-// k_ingest_tensor of t into dst, queued as ingest_queue below queues a picture's kernel
-static int ingest_queue_tensor(jmh_ctx *c, const jmh_device_tensor *t, uint8_t *dst, hipEvent_t ev) {
-    if (t->stream) {
-        HCHK(hipEventRecord(ev, (hipStream_t)t->stream));
-        HCHK(hipStreamWaitEvent(c->st, ev, 0));
-    }
-    uint8_t *out = dst;
-    int W = c->W, H = c->H, r;
-    ScaleTab *tab = nullptr;
-    if (c->scale.filter != JMH_SCALE_OFF && (r = scale_begin(c, t->width, t->height, &out, &W, &H, &tab))) return r;
-    TensorArgs g;
-    for (int i = 0; i < 3; i++) g.chan[i] = (const uint8_t *)t->chan[i];
-    g.sx = t->stride_x; g.sy = t->stride_y;
-    g.dst = out; g.w = t->width; g.h = t->height; g.W = W; g.H = H;
-    jmr_coefficients(t->flags, c->bd, &g.k);
-    HCHK(jmh_launch_ingest_tensor(t->dtype, g, c->st));
-    return tab ? scale_end(c, tab, t->width, t->height, W, H, dst) : JMH_OK;
-}
-
-// k_ingest of p into dst on the context's stream, behind the work queued on the caller's stream so
-// far (ev: that stream's event); slot: the clamp word of an I010 picture
-static int ingest_queue(jmh_ctx *c, const jmh_device_picture *p, uint8_t *dst, int slot, hipEvent_t ev) {
-    if (p->stream) {
-        HCHK(hipEventRecord(ev, (hipStream_t)p->stream));
-        HCHK(hipStreamWaitEvent(c->st, ev, 0));
-    }
-    uint8_t *out = dst;
-    int W = c->W, H = c->H, r;
-    ScaleTab *tab = nullptr;
-    if (c->scale.filter != JMH_SCALE_OFF && (r = scale_begin(c, p->width, p->height, &out, &W, &H, &tab))) return r;
-    if (jmr_is_rgb(p->format)) {   // k_ingest_rgb: one plane, nothing counted
-        RgbArgs g;
-        g.src = (const uint8_t *)p->plane[0]; g.stride = p->stride[0];
-        g.dst = out; g.w = p->width; g.h = p->height; g.W = W; g.H = H;
-        jmr_coefficients(p->format, c->bd, &g.k);
-        HCHK(jmh_launch_ingest_rgb(p->format, g, c->st));
-        return tab ? scale_end(c, tab, p->width, p->height, W, H, dst) : JMH_OK;
-    }
-    unsigned long long *clamped = nullptr;
-    const bool counts = device_format_counts(p->format);
-    if (counts) {
-        const size_t nb = (size_t)(c->nring + 1) * sizeof(unsigned long long);
-        if (!c->d_clamp && hipMalloc((void **)&c->d_clamp, nb) != hipSuccess) { c->d_clamp = nullptr; return JMH_E_OOM; }
-        if (!c->h_clamp && hipHostMalloc((void **)&c->h_clamp, nb, hipHostMallocDefault) != hipSuccess) { c->h_clamp = nullptr; return JMH_E_OOM; }
-        clamped = c->d_clamp + slot;
-        HCHK(hipMemsetAsync(clamped, 0, sizeof(unsigned long long), c->st));
-    }
-    if (jmy_is_yuv(p->format)) {   // k_ingest_yuv: 4:2:2 / 4:4:4 reduced to 4:2:0 (planes the layout does not read stay null)
-        YuvArgs g;
-        for (int i = 0; i < 3; i++) {
-            const bool read = i < jmy_planes(jmy_layout(p->format));
-            g.plane[i] = read ? (const uint8_t *)p->plane[i] : nullptr; g.stride[i] = read ? p->stride[i] : 0;
-        }
-        g.dst = out; g.w = p->width; g.h = p->height; g.W = W; g.H = H; g.maxv = (uint32_t)c->maxv; g.clamped = clamped;
-        HCHK(jmh_launch_ingest_yuv(p->format, g, c->st));
-    } else {
-        IngestArgs a;
-        for (int i = 0; i < 3; i++) { a.plane[i] = (const uint8_t *)p->plane[i]; a.stride[i] = p->stride[i]; }
-        a.dst = out; a.w = p->width; a.h = p->height; a.W = W; a.H = H; a.maxv = (uint32_t)c->maxv; a.clamped = clamped;
-        HCHK(jmh_launch_ingest(p->format, a, c->st));
-    }
-    if (counts) HCHK(hipMemcpyAsync(c->h_clamp + slot, clamped, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->st));
-    return tab ? scale_end(c, tab, p->width, p->height, W, H, dst) : JMH_OK;
-}
+// the source of a pushed picture: host planes (strides in samples) or a device source
+struct PushSrc { const void *y, *u, *v; int sy, sc; bool wide; DevSrc dev; };
 
 static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *fp, const CodedPush *cp = nullptr) {
     if (!c || !fp) return JMH_E_INVALID_ARG;
     const bool armed = c->nal_armed && cp;   // jmh_coded_nal_heads holds for one push, whatever becomes of it
     c->nal_armed = false;
     int r;
-    void *const in_stream = s.dev ? s.dev->stream : s.ten ? s.ten->stream : nullptr;   // the caller's, of a device source
-    const bool device_src = s.dev || s.ten;
-    if (s.dev) { if ((r = check_device_pic(c, s.dev))) return r; }
-    else if (s.ten) { if ((r = check_device_tensor(c, s.ten))) return r; }
+    const bool device_src = (bool)s.dev;
+    void *const in_stream = device_src ? s.dev.stream() : nullptr;   // the caller's, of a device source
+    if (device_src) { if ((r = devsrc_check(c, s.dev))) return r; }
     else if (!s.y || !s.u || !s.v || s.sy < c->W || s.sc < c->Wc) return JMH_E_INVALID_ARG;
     if ((r = check_params(c, fp))) return r;
-    if ((r = s.dev ? (device_depth_ok(c, s.dev->format) ? JMH_OK : JMH_E_UNSUPPORTED_CFG)
-           : s.ten ? (jmt_depth_ok(s.ten->dtype, c->bd) ? JMH_OK : JMH_E_UNSUPPORTED_CFG) : check_pic(c, s.wide))) return r;
+    if ((r = device_src ? devsrc_depth(c, s.dev) : check_pic(c, s.wide))) return r;
     std::vector<uint8_t> descs;
     if (cp) {   // before anything is claimed or queued
         if (cp->cw <= 0 || cp->ch <= 0 || cp->cw > c->W || cp->ch > c->H) return JMH_E_INVALID_ARG;
@@ -1483,7 +1036,7 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
         // is given after this call may overwrite the planes
         if (in_stream && !b.ev_in && hipEventCreateWithFlags(&b.ev_in, hipEventDisableTiming) != hipSuccess) { b.ev_in = nullptr; return JMH_E_HIP; }
         HCHK(hipEventRecord(b.ev_t0, c->st));
-        if ((r = s.dev ? ingest_queue(c, s.dev, b.src, e, b.ev_in) : ingest_queue_tensor(c, s.ten, b.src, b.ev_in))) return r;
+        if ((r = ingest_queue(c, s.dev, b.src, e, b.ev_in))) return r;
         HCHK(hipEventRecord(b.ev_src, c->st));
         if (in_stream) HCHK(hipStreamWaitEvent((hipStream_t)in_stream, b.ev_src, 0));
         c->last_dev_entry = e;
@@ -1497,7 +1050,7 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
         HCHK(hipMemcpyAsync(b.src, b.h_src, c->fsize, hipMemcpyHostToDevice, c->st));
         HCHK(hipEventRecord(b.ev_src, c->st));
     }
-    b.dev_fmt = s.dev ? s.dev->format + 1 : 0;
+    b.dev_fmt = s.dev.pic ? s.dev.pic->format + 1 : 0;
     b.coded = cp != nullptr;
     if (cp) {
         const CodedLayout L(c->nmb);
@@ -1510,110 +1063,6 @@ static int frame_push_any(jmh_ctx *c, const PushSrc &s, const jmh_frame_params *
     c->popq.push_back(e);
     return push_picture(c, b.src, e, fp, 1);
 }
-extern "C" {
-int jmh_frame_push(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp) {
-    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, nullptr, nullptr}, fp);
-}
-int jmh_frame_push_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp) {
-    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, nullptr, nullptr}, fp);
-}
-
-int jmh_frame_push_coded(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp, int n,
-                         const jmh_coded_slice *slices, int crop_w, int crop_h) {
-    const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, nullptr, nullptr}, fp, &cp);
-}
-int jmh_frame_push_coded_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp,
-                             int n, const jmh_coded_slice *slices, int crop_w, int crop_h) {
-    const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, nullptr, nullptr}, fp, &cp);
-}
-
-// ---- pictures that are already on the device (include/jmhip_input.h) ----
-int jmh_frame_push_device(jmh_ctx *c, const jmh_device_picture *pic, const jmh_frame_params *fp) {
-    if (!pic) return JMH_E_INVALID_ARG;
-    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, pic, nullptr}, fp);
-}
-int jmh_frame_push_coded_device(jmh_ctx *c, const jmh_device_picture *pic, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
-                                int crop_w, int crop_h) {
-    if (!pic) return JMH_E_INVALID_ARG;
-    const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, pic, nullptr}, fp, &cp);
-}
-// ---- tensors that are already on the device (include/jmhip_tensor.h) ----
-int jmh_frame_push_tensor(jmh_ctx *c, const jmh_device_tensor *t, const jmh_frame_params *fp) {
-    if (!t) return JMH_E_INVALID_ARG;
-    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, nullptr, t}, fp);
-}
-int jmh_frame_push_coded_tensor(jmh_ctx *c, const jmh_device_tensor *t, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
-                                int crop_w, int crop_h) {
-    if (!t) return JMH_E_INVALID_ARG;
-    const CodedPush cp = {n, slices, crop_w, crop_h};
-    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, nullptr, t}, fp, &cp);
-}
-int jmh_device_input_wait(jmh_ctx *c) {
-    if (!c) return JMH_E_INVALID_ARG;
-    if (c->last_dev_entry < 0) return JMH_OK;
-    HCHK(hipSetDevice(c->dev));
-    HCHK(hipEventSynchronize(c->ring[c->last_dev_entry].ev_src));   // (a later occupant's event has passed the picture's too)
-    return JMH_OK;
-}
-int jmh_device_input_clamped(const jmh_ctx *c, uint64_t *n) {
-    if (!c || !n) return JMH_E_INVALID_ARG;
-    *n = c->last_clamped;
-    return JMH_OK;
-}
-int jmh_device_malloc(jmh_ctx *c, size_t n, void **p) {
-    if (!c || !p || !n) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    if (hipMalloc(p, n) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return JMH_E_OOM; }
-    return JMH_OK;
-}
-int jmh_device_free(jmh_ctx *c, void *p) {
-    if (!c) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    if (p) HCHK(hipFree(p));
-    return JMH_OK;
-}
-int jmh_device_upload(jmh_ctx *c, void *dst, const void *src, size_t n, void *stream) {
-    if (!c || !dst || !src) return JMH_E_INVALID_ARG;
-    if (!n) return JMH_OK;
-    HCHK(hipSetDevice(c->dev));
-    if (!stream) {
-        HCHK(hipMemcpy(dst, src, n, hipMemcpyHostToDevice));
-        return JMH_OK;
-    }
-    // through the context's pinned buffer: src is free on return, the copy itself runs on the stream
-    if (!c->ev_up) { if (hipEventCreateWithFlags(&c->ev_up, hipEventDisableTiming) != hipSuccess) { c->ev_up = nullptr; return JMH_E_HIP; } }
-    else HCHK(hipEventSynchronize(c->ev_up));
-    if (n > c->up_cap) {
-        if (c->up_h) (void)hipHostFree(c->up_h);
-        c->up_h = nullptr; c->up_cap = 0;
-        if (hipHostMalloc((void **)&c->up_h, n, hipHostMallocDefault) != hipSuccess) { c->up_h = nullptr; return JMH_E_OOM; }
-        c->up_cap = n;
-    }
-    memcpy(c->up_h, src, n);
-    HCHK(hipMemcpyAsync(dst, c->up_h, n, hipMemcpyHostToDevice, (hipStream_t)stream));
-    HCHK(hipEventRecord(c->ev_up, (hipStream_t)stream));
-    return JMH_OK;
-}
-int jmh_device_stream_create(jmh_ctx *c, void **stream) {
-    if (!c || !stream) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    hipStream_t st = nullptr;
-    HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    *stream = st;
-    return JMH_OK;
-}
-int jmh_device_stream_destroy(jmh_ctx *c, void *stream) {
-    if (!c || !stream) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    HCHK(hipStreamSynchronize((hipStream_t)stream));
-    HCHK(hipStreamDestroy((hipStream_t)stream));
-    return JMH_OK;
-}
-
-}  // extern "C"
 // the pop's wait for ring entry e, the oldest picture not yet popped
 static int pop_wait(jmh_ctx *c, int e) {
     int r = issue_while(c, [c, e] {
@@ -1750,7 +1199,236 @@ static int pop_coded_nal(jmh_ctx *c, int e, uint8_t *out, size_t cap, jmh_coded_
     return JMH_OK;
 }
 
+static int read_pic(jmh_ctx *c, void *y, void *u, void *v, int sy, int sc, bool wide, bool dbk) {
+    if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
+    if ((c->bd > 8) != wide) return JMH_E_UNSUPPORTED_CFG;
+    if (c->cur_entry >= 0 && c->ring[c->cur_entry].coded) {   // not read back at its pop: from the entry's device buffers, on demand
+        const PicBuf &b = c->ring[c->cur_entry];
+        if (dbk && !b.deblocked) return JMH_E_STATE;
+        HCHK(hipSetDevice(c->dev));
+        if (!c->h_coded_pic && hipHostMalloc((void **)&c->h_coded_pic, c->fsize, hipHostMallocDefault) != hipSuccess) { c->h_coded_pic = nullptr; return JMH_E_OOM; }
+        HCHK(hipMemcpyAsync(c->h_coded_pic, dbk ? b.dbk : b.rec, c->fsize, hipMemcpyDeviceToHost, c->cst));
+        HCHK(hipStreamSynchronize(c->cst));
+        unpack_planes(c->h_coded_pic, c->W, c->H, y, u, v, sy, sc, c->ps);
+        return JMH_OK;
+    }
+    if (c->cur_entry < 0 || !(dbk ? c->ring[c->cur_entry].deblocked : c->ring[c->cur_entry].recon_read)) return JMH_E_STATE;
+    const PicBuf &b = c->ring[c->cur_entry];
+    unpack_planes(dbk ? b.h_dbk : b.h_rec, c->W, c->H, y, u, v, sy, sc, c->ps);
+    return JMH_OK;
+}
+static int load_frame_any(jmh_ctx *c, int slot, const void *y, const void *u, const void *v, int sy, int sc, bool wide) {
+    if (!c || slot < 0 || slot >= c->nslots || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
+    int r = check_pic(c, wide);
+    if (r) return r;
+    HCHK(hipSetDevice(c->dev));
+    r = drain(c);   // pictures in flight may read the slot
+    if (r) return r;
+    HCHK(hipStreamSynchronize(c->st));
+    if (!pack_planes(c->h_stage_ref, c->W, c->H, y, u, v, sy, sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
+    HCHK(hipMemcpyAsync(c->d_slots + (size_t)slot * c->fsize, c->h_stage_ref, c->fsize, hipMemcpyHostToDevice, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+
+// ---- the unit seams, one helper each for both sample widths (pel = uint8_t: the 8-bit entries,
+//      uint16_t: the High 10 ..._u16 ones, which range-check their samples on the host) ----------
+// SetupFastFullPelSearch's SAD table.  8 bits: slot 0 against the current reference, after the
+// pictures in flight; 16 bits: the search pictures (jmh_search_pictures_u16), centres within +-SR
+template <class pel>
+static int sad_table(jmh_ctx *c, int n_mb, const int32_t *mb_xy, const int32_t *centres, uint16_t *out) {
+    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
+    if (!c || n_mb <= 0 || !mb_xy || !centres || !out) return JMH_E_INVALID_ARG;
+    for (int i = 0; i < n_mb; i++)
+        if (mb_xy[2 * i] < 0 || mb_xy[2 * i] >= c->mbw || mb_xy[2 * i + 1] < 0 || mb_xy[2 * i + 1] >= c->mbh ||
+            (wi && (abs(centres[2 * i]) > c->sr || abs(centres[2 * i + 1]) > c->sr))) return JMH_E_INVALID_ARG;
+    const pel *org, *ref;
+    if constexpr (wi) {
+        if (!c->spic[wi].cur) return JMH_E_STATE;
+        HCHK(hipSetDevice(c->dev));
+        org = (const pel *)c->spic[wi].cur; ref = (const pel *)c->spic[wi].ref;
+    } else {
+        if (c->ref_kind == REF_NONE) return JMH_E_STATE;
+        if (c->bd > 8) return JMH_E_UNSUPPORTED_CFG;   // the 8-bit SAD-table seam (High 10: jmh_ffs_sad_table_u16)
+        HCHK(hipSetDevice(c->dev));
+        int r = drain(c);
+        if (r) return r;
+        org = c->d_slots; ref = ref_ptr(c);
+    }
+    int32_t *d_xy = nullptr, *d_c = nullptr;
+    uint16_t *d_out = nullptr;
+    const size_t on = (size_t)n_mb * 16 * c->npos;
+    DevTemps tmp;
+    HCHK(tmp.alloc(&d_xy, n_mb * 8));
+    HCHK(tmp.alloc(&d_c, n_mb * 8));
+    HCHK(tmp.alloc(&d_out, on * 2));
+    HCHK(hipMemcpyAsync(d_xy, mb_xy, n_mb * 8, hipMemcpyHostToDevice, c->st));
+    HCHK(hipMemcpyAsync(d_c, centres, n_mb * 8, hipMemcpyHostToDevice, c->st));
+    HCHK(jmh_launch_sad_table(org, ref, c->W, c->H, c->sr, n_mb, d_xy, d_c, d_out, c->st));
+    HCHK(hipMemcpyAsync(out, d_out, on * 2, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+
+// dct_luma / dct_luma8x8 at bit_depth (EL = 16 or 64 samples per block)
+template <int EL, class pel>
+static int tq_batch(jmh_ctx *c, int n, const int16_t *resid, const pel *pred, int qp, int intra, int bit_depth, int16_t *levels, pel *recon,
+                    int32_t *coeff_cost, int32_t *nonzero) {
+    if (!c || n <= 0 || !resid || !pred || !levels || !recon || !coeff_cost || !nonzero || qp < 0 || qp > 51 || bit_depth < 8 ||
+        bit_depth > 10) return JMH_E_INVALID_ARG;
+    const int maxv = (1 << bit_depth) - 1;
+    if constexpr (sizeof(pel) == 2)
+        for (size_t k = 0; k < (size_t)n * EL; k++)   // the int32 headroom of the quantiser assumes these ranges
+            if (pred[k] > maxv || resid[k] > maxv || resid[k] < -maxv) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    int16_t *dr, *dl;
+    pel *dp, *drec;
+    int32_t *dcc, *dnz;
+    const size_t cb = (size_t)n * EL * 2, sb = (size_t)n * EL * sizeof(pel);   // bytes of the coefficients, of the samples
+    DevTemps tmp;
+    HCHK(tmp.alloc(&dr, cb)); HCHK(tmp.alloc(&dl, cb));
+    HCHK(tmp.alloc(&dp, sb)); HCHK(tmp.alloc(&drec, sb));
+    HCHK(tmp.alloc(&dcc, (size_t)n * 4)); HCHK(tmp.alloc(&dnz, (size_t)n * 4));
+    HCHK(hipMemcpyAsync(dr, resid, cb, hipMemcpyHostToDevice, c->st));
+    HCHK(hipMemcpyAsync(dp, pred, sb, hipMemcpyHostToDevice, c->st));
+    const int qpb = qp + 6 * (bit_depth - 8), qsel = q_selector(c->cfg, intra != 0);
+    if (EL == 16) HCHK(jmh_launch_tq4x4(n, dr, dp, qpb, qsel, maxv, dl, drec, dcc, dnz, c->st));
+    else HCHK(jmh_launch_tq8x8(n, dr, dp, qpb, qsel, maxv, dl, drec, dcc, dnz, c->st));
+    HCHK(hipMemcpyAsync(levels, dl, cb, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipMemcpyAsync(recon, drec, sb, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipMemcpyAsync(coeff_cost, dcc, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipMemcpyAsync(nonzero, dnz, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+
+// the luma pictures of the per-block searches (the 16-bit ones record their bit depth)
+template <class pel>
+static int search_pictures(jmh_ctx *c, const pel *cur_y, const pel *ref_y, int sy, int bit_depth) {
+    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
+    if (!c || !cur_y || !ref_y || sy < c->W || bit_depth < 8 || bit_depth > 10) return JMH_E_INVALID_ARG;
+    if constexpr (wi) {
+        const int maxv = (1 << bit_depth) - 1;
+        for (int y = 0; y < c->H; y++)   // out-of-range samples would break the 19-bit cost keys
+            for (int x = 0; x < c->W; x++)
+                if (cur_y[(size_t)y * sy + x] > maxv || ref_y[(size_t)y * sy + x] > maxv) return JMH_E_INVALID_ARG;
+    }
+    HCHK(hipSetDevice(c->dev));
+    auto &sp = c->spic[wi];
+    const size_t row = (size_t)c->W * sizeof(pel);
+    if (!sp.cur) {
+        if (hipMalloc(&sp.cur, row * c->H) != hipSuccess) return JMH_E_OOM;
+        if (hipMalloc(&sp.ref, row * c->H) != hipSuccess) { (void)hipFree(sp.cur); sp.cur = nullptr; return JMH_E_OOM; }
+    }
+    HCHK(hipStreamSynchronize(c->st));   // an earlier search may still read the buffers
+    HCHK(hipMemcpy2DAsync(sp.cur, row, cur_y, (size_t)sy * sizeof(pel), row, c->H, hipMemcpyHostToDevice, c->st));
+    HCHK(hipMemcpy2DAsync(sp.ref, row, ref_y, (size_t)sy * sizeof(pel), row, c->H, hipMemcpyHostToDevice, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    if (wi) c->hbd_bits = bit_depth;
+    return JMH_OK;
+}
+
+static int check_block_requests(const jmh_ctx *c, int n, const jmh_block_search *req) {
+    for (int i = 0; i < n; i++) {   // the kernel's block and window assumptions, checked on the host
+        const jmh_block_search &q = req[i];
+        if (q.blocktype < 1 || q.blocktype > 7 || q.mb_x < 0 || q.mb_x >= c->mbw || q.mb_y < 0 || q.mb_y >= c->mbh) return JMH_E_INVALID_ARG;
+        static const int bw4[8] = {4, 4, 4, 2, 2, 2, 1, 1}, bh4[8] = {4, 4, 2, 4, 2, 1, 2, 1};
+        if (q.block_x < 0 || q.block_y < 0 || q.block_x + bw4[q.blocktype] > 4 || q.block_y + bh4[q.blocktype] > 4) return JMH_E_INVALID_ARG;
+        if (q.search_range < 0 || q.search_range > c->sr) return JMH_E_INVALID_ARG;
+        if (q.search_range > SRMAX) return JMH_E_UNSUPPORTED_CFG;   // 13-bit spiral order keys: (2 SR + 1)^2 < 8192
+        if (q.lambda_factor < 0 || q.lambda_factor > (1 << 24)) return JMH_E_INVALID_ARG;
+        if (q.search_mode != 0 && q.search_mode != -1) return JMH_E_UNSUPPORTED_CFG;
+        if (abs(q.centre[0]) > 2048 || abs(q.centre[1]) > 2048 || abs(q.pred_mv[0]) > 8192 || abs(q.pred_mv[1]) > 8192) return JMH_E_INVALID_ARG;
+    }
+    return JMH_OK;
+}
+// BlockMotionSearch per request on the search pictures of pel's width; maxv = 2^(their bit depth) - 1
+template <class pel>
+static int block_motion_search(jmh_ctx *c, int n, const jmh_block_search *req, jmh_block_result *res, int maxv) {
+    if (!c || n <= 0 || !req || !res) return JMH_E_INVALID_ARG;
+    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
+    const auto &sp = c->spic[wi];
+    if (!sp.cur) return JMH_E_STATE;
+    int r = check_block_requests(c, n, req);
+    if (r) return r;
+    HCHK(hipSetDevice(c->dev));
+    DevTemps tmp;
+    jmh_block_search *d_req;
+    jmh_block_result *d_res;
+    HCHK(tmp.alloc(&d_req, (size_t)n * sizeof(jmh_block_search)));
+    HCHK(tmp.alloc(&d_res, (size_t)n * sizeof(jmh_block_result)));
+    HCHK(hipMemcpyAsync(d_req, req, (size_t)n * sizeof(jmh_block_search), hipMemcpyHostToDevice, c->st));
+    HCHK(jmh_launch_block_search(n, d_req, d_res, (const pel *)sp.cur, (const pel *)sp.ref, c->W, c->H, c->cfg.use_hadamard, maxv, c->st));
+    HCHK(hipMemcpyAsync(res, d_res, (size_t)n * sizeof(jmh_block_result), hipMemcpyDeviceToHost, c->st));
+    HCHK(hipStreamSynchronize(c->st));
+    return JMH_OK;
+}
+// ---- references, pushes, pops, the writers and the unit seams ----
 extern "C" {
+int jmh_set_reference(jmh_ctx *c, int list, int ref_idx, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc) {
+    return set_reference_any(c, list, ref_idx, y, u, v, sy, sc, false);
+}
+int jmh_set_reference_u16(jmh_ctx *c, int list, int ref_idx, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc) {
+    return set_reference_any(c, list, ref_idx, y, u, v, sy, sc, true);
+}
+
+int jmh_set_reference_slot(jmh_ctx *c, int slot) {
+    if (!c || slot < -2 || slot >= c->nslots) return JMH_E_INVALID_ARG;
+    HCHK(hipSetDevice(c->dev));
+    if (slot < 0) {   // the last pushed picture (its recon, or its device deblocking): no copy
+        if (c->last_id < 0 || (slot == -2 && !c->ring[c->last_entry].deblocked)) return JMH_E_STATE;
+        c->ref_kind = slot == -1 ? REF_REC : REF_DBK;
+        c->ref_entry = c->last_entry;
+        return JMH_OK;
+    }
+    int r = drain(c);
+    if (r) return r;
+    HCHK(hipMemcpyAsync(c->d_ref, c->d_slots + (size_t)slot * c->fsize, c->fsize, hipMemcpyDeviceToDevice, c->st));
+    c->ref_kind = REF_BUF; c->ref_entry = -1;
+    return JMH_OK;
+}
+
+int jmh_frame_push(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp) {
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, {}}, fp);
+}
+int jmh_frame_push_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp) {
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, {}}, fp);
+}
+
+int jmh_frame_push_coded(jmh_ctx *c, const uint8_t *y, const uint8_t *u, const uint8_t *v, int sy, int sc, const jmh_frame_params *fp, int n,
+                         const jmh_coded_slice *slices, int crop_w, int crop_h) {
+    const CodedPush cp = {n, slices, crop_w, crop_h};
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, false, {}}, fp, &cp);
+}
+int jmh_frame_push_coded_u16(jmh_ctx *c, const uint16_t *y, const uint16_t *u, const uint16_t *v, int sy, int sc, const jmh_frame_params *fp,
+                             int n, const jmh_coded_slice *slices, int crop_w, int crop_h) {
+    const CodedPush cp = {n, slices, crop_w, crop_h};
+    return frame_push_any(c, PushSrc{y, u, v, sy, sc, true, {}}, fp, &cp);
+}
+
+// ---- pictures that are already on the device (include/jmhip_input.h) ----
+int jmh_frame_push_device(jmh_ctx *c, const jmh_device_picture *pic, const jmh_frame_params *fp) {
+    if (!pic) return JMH_E_INVALID_ARG;
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, {pic, nullptr}}, fp);
+}
+int jmh_frame_push_coded_device(jmh_ctx *c, const jmh_device_picture *pic, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
+                                int crop_w, int crop_h) {
+    if (!pic) return JMH_E_INVALID_ARG;
+    const CodedPush cp = {n, slices, crop_w, crop_h};
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, {pic, nullptr}}, fp, &cp);
+}
+// ---- tensors that are already on the device (include/jmhip_tensor.h) ----
+int jmh_frame_push_tensor(jmh_ctx *c, const jmh_device_tensor *t, const jmh_frame_params *fp) {
+    if (!t) return JMH_E_INVALID_ARG;
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, {nullptr, t}}, fp);
+}
+int jmh_frame_push_coded_tensor(jmh_ctx *c, const jmh_device_tensor *t, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
+                                int crop_w, int crop_h) {
+    if (!t) return JMH_E_INVALID_ARG;
+    const CodedPush cp = {n, slices, crop_w, crop_h};
+    return frame_push_any(c, PushSrc{nullptr, nullptr, nullptr, 0, 0, false, {nullptr, t}}, fp, &cp);
+}
+
 int jmh_nal_geometry(int *tile_bytes, int *chunk_bytes) {
     if (!tile_bytes || !chunk_bytes) return JMH_E_INVALID_ARG;
     *tile_bytes = JMN_TILE; *chunk_bytes = JMN_CHUNK;
@@ -1899,268 +1577,9 @@ int jmh_cabac_split_stats(const jmh_ctx *c, jmh_cabac_split_info *out) {
     return JMH_OK;
 }
 
-}  // extern "C"
-static int read_pic(jmh_ctx *c, void *y, void *u, void *v, int sy, int sc, bool wide, bool dbk) {
-    if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
-    if ((c->bd > 8) != wide) return JMH_E_UNSUPPORTED_CFG;
-    if (c->cur_entry >= 0 && c->ring[c->cur_entry].coded) {   // not read back at its pop: from the entry's device buffers, on demand
-        const PicBuf &b = c->ring[c->cur_entry];
-        if (dbk && !b.deblocked) return JMH_E_STATE;
-        HCHK(hipSetDevice(c->dev));
-        if (!c->h_coded_pic && hipHostMalloc((void **)&c->h_coded_pic, c->fsize, hipHostMallocDefault) != hipSuccess) { c->h_coded_pic = nullptr; return JMH_E_OOM; }
-        HCHK(hipMemcpyAsync(c->h_coded_pic, dbk ? b.dbk : b.rec, c->fsize, hipMemcpyDeviceToHost, c->cst));
-        HCHK(hipStreamSynchronize(c->cst));
-        unpack_planes(c->h_coded_pic, c->W, c->H, y, u, v, sy, sc, c->ps);
-        return JMH_OK;
-    }
-    if (c->cur_entry < 0 || !(dbk ? c->ring[c->cur_entry].deblocked : c->ring[c->cur_entry].recon_read)) return JMH_E_STATE;
-    const PicBuf &b = c->ring[c->cur_entry];
-    unpack_planes(dbk ? b.h_dbk : b.h_rec, c->W, c->H, y, u, v, sy, sc, c->ps);
-    return JMH_OK;
-}
-static int load_frame_any(jmh_ctx *c, int slot, const void *y, const void *u, const void *v, int sy, int sc, bool wide) {
-    if (!c || slot < 0 || slot >= c->nslots || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
-    int r = check_pic(c, wide);
-    if (r) return r;
-    HCHK(hipSetDevice(c->dev));
-    r = drain(c);   // pictures in flight may read the slot
-    if (r) return r;
-    HCHK(hipStreamSynchronize(c->st));
-    if (!pack_planes(c->h_stage_ref, c->W, c->H, y, u, v, sy, sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
-    HCHK(hipMemcpyAsync(c->d_slots + (size_t)slot * c->fsize, c->h_stage_ref, c->fsize, hipMemcpyHostToDevice, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
-}
-
-// jmhip_scale.h: the sticky setting of the device pushes, its tables on the host, the setting read back
-extern "C" int jmh_input_scale(jmh_ctx *c, const jmh_scale *s) {
-    if (!c) return JMH_E_INVALID_ARG;
-    if (!s || s->filter == JMH_SCALE_OFF) { c->scale = jmh_scale{0, 0, 0, 0}; return JMH_OK; }
-    if (jms_check_setting(s->filter, s->flags, s->out_width, s->out_height, c->W, c->H)) return JMH_E_INVALID_ARG;
-    c->scale = *s;
-    return JMH_OK;
-}
-extern "C" int jmh_scale_taps(int n_src, int n_dst, int filter, int chroma_left, int32_t *first, int16_t *taps, int *ntaps) {
-    return jms_taps(n_src, n_dst, filter, chroma_left != 0, first, taps, ntaps);
-}
-extern "C" int jmh_scale_info(const jmh_ctx *c, jmh_scale *s, int *active) {
-    if (!c || !s || !active) return JMH_E_INVALID_ARG;
-    *s = c->scale;
-    *active = c->scale.filter != JMH_SCALE_OFF;
-    return JMH_OK;
-}
-
-// the unit seam of k_ingest: the kernel into a scratch picture, the packed planes to the host
-extern "C" int jmh_ingest_picture(jmh_ctx *c, const jmh_device_picture *pic, void *y, void *u, void *v, int sy, int sc) {
-    if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
-    int r = check_device_pic(c, pic);
-    if (r) return r;
-    if (!device_depth_ok(c, pic->format)) return JMH_E_UNSUPPORTED_CFG;
-    HCHK(hipSetDevice(c->dev));
-    DevTemps t;
-    uint8_t *d = nullptr;
-    if (t.alloc(&d, c->fsize) != hipSuccess) return JMH_E_OOM;
-    hipEvent_t ev = nullptr;
-    if (pic->stream) HCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    r = ingest_queue(c, pic, d, c->nring, ev);
-    if (!r && pic->stream && (hipEventRecord(ev, c->st) != hipSuccess || hipStreamWaitEvent((hipStream_t)pic->stream, ev, 0) != hipSuccess))
-        r = JMH_E_HIP;
-    const hipError_t se = hipStreamSynchronize(c->st);
-    if (ev) (void)hipEventDestroy(ev);
-    if (r) return r;
-    HCHK(se);
-    std::vector<uint8_t> h(c->fsize);
-    HCHK(hipMemcpy(h.data(), d, c->fsize, hipMemcpyDeviceToHost));
-    unpack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps);
-    c->last_clamped = device_format_counts(pic->format) ? c->h_clamp[c->nring] : 0;
-    return JMH_OK;
-}
-
-// the unit seam of k_ingest_tensor: the kernel into a scratch picture, the packed planes to the host
-extern "C" int jmh_ingest_tensor(jmh_ctx *c, const jmh_device_tensor *t, void *y, void *u, void *v, int sy, int sc) {
-    if (!c || !y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
-    int r = check_device_tensor(c, t);
-    if (r) return r;
-    if (!jmt_depth_ok(t->dtype, c->bd)) return JMH_E_UNSUPPORTED_CFG;
-    HCHK(hipSetDevice(c->dev));
-    DevTemps tmp;
-    uint8_t *d = nullptr;
-    if (tmp.alloc(&d, c->fsize) != hipSuccess) return JMH_E_OOM;
-    hipEvent_t ev = nullptr;
-    if (t->stream) HCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    r = ingest_queue_tensor(c, t, d, ev);
-    if (!r && t->stream && (hipEventRecord(ev, c->st) != hipSuccess || hipStreamWaitEvent((hipStream_t)t->stream, ev, 0) != hipSuccess))
-        r = JMH_E_HIP;
-    const hipError_t se = hipStreamSynchronize(c->st);
-    if (ev) (void)hipEventDestroy(ev);
-    if (r) return r;
-    HCHK(se);
-    std::vector<uint8_t> h(c->fsize);
-    HCHK(hipMemcpy(h.data(), d, c->fsize, hipMemcpyDeviceToHost));
-    unpack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps);
-    c->last_clamped = 0;
-    return JMH_OK;
-}
-
-// the quantiser of a tensor's elements (include/jmhip_tensor.h) on the host: needs no context
-extern "C" int jmh_tensor_quantise(int dtype, int bit_depth, const void *elems, size_t n, int32_t *q) {
-    if (dtype < 0 || dtype >= JMT_NDTYPES || (n && (!elems || !q))) return JMH_E_INVALID_ARG;
-    if (!jmt_depth_ok(dtype, bit_depth)) return JMH_E_UNSUPPORTED_CFG;
-    const int32_t M = (1 << bit_depth) - 1;
-    const uint8_t *p = (const uint8_t *)elems;
-    for (size_t i = 0; i < n; i++) q[i] = jmt_quant(dtype, jmt_load(dtype, p + i * jmt_es(dtype)), M);
-    return JMH_OK;
-}
-
-// ---- decoded pictures pulled on the device (include/jmhip_output.h) ----
-// the destination of a pull: a picture or a tensor
-struct PullDst { const jmh_device_picture_out *pic; const jmh_device_tensor_out *ten; };
-
-// the argument rules, then the context's bit depth
-static int check_pull_dst(const jmh_ctx *c, const PullDst &d) {
-    if (d.pic) {
-        const jmh_device_picture_out *p = d.pic;
-        if (jmout_check_picture(p->format, p->width, p->height, c->W, c->H, p->plane, p->stride)) return JMH_E_INVALID_ARG;
-        return jmout_picture_depth_ok(p->format, c->bd) ? JMH_OK : JMH_E_UNSUPPORTED_CFG;
-    }
-    const jmh_device_tensor_out *t = d.ten;
-    if (!t || jmout_check_tensor(t->dtype, t->flags, t->width, t->height, c->W, c->H, t->chan, t->stride_x, t->stride_y)) return JMH_E_INVALID_ARG;
-    return jmout_tensor_depth_ok(t->dtype, c->bd) ? JMH_OK : JMH_E_UNSUPPORTED_CFG;
-}
-static int output_stream(jmh_ctx *c) {
-    if (!c->ost && hipStreamCreateWithFlags(&c->ost, hipStreamNonBlocking) != hipSuccess) { c->ost = nullptr; return JMH_E_HIP; }
-    return JMH_OK;
-}
-// the one kernel of a (checked) destination, reading the packed picture at src, on st
-static int pull_launch(jmh_ctx *c, const PullDst &d, const uint8_t *src, hipStream_t st) {
-    OutArgs a;
-    a.src = src; a.W = c->W; a.H = c->H;
-    if (d.pic) {
-        const jmh_device_picture_out *p = d.pic;
-        for (int i = 0; i < 3; i++) { a.dst[i] = (uint8_t *)p->plane[i]; a.stride[i] = p->stride[i]; }
-        a.w = p->width; a.h = p->height;
-        jmout_coefficients(p->format, c->bd, &a.k);   // a YUV format reads none of them
-        HCHK(jmh_launch_pull_picture(p->format, a, st));
-    } else {
-        const jmh_device_tensor_out *t = d.ten;
-        for (int i = 0; i < 3; i++) a.dst[i] = (uint8_t *)t->chan[i];
-        a.stride[0] = t->stride_x; a.stride[1] = t->stride_y; a.stride[2] = 0;
-        a.w = t->width; a.h = t->height;
-        jmout_coefficients(t->flags, c->bd, &a.k);
-        HCHK(jmh_launch_pull_tensor(t->dtype, a, st));
-    }
-    return JMH_OK;
-}
-// jmh_pull_picture / jmh_pull_tensor.  The current picture is complete (its pop waited for it), so the
-// kernel waits for nothing but its stream: the caller's, where it is ordered behind the destination's
-// last consumer and in front of its next one, or the context's own, waited for here.  The entry's
-// event then holds the pull, for the claim that rewrites the entry (claim_entry) and for output_wait;
-// an earlier pull of the entry on another stream is chained in front, so one event holds them all.
-static int pull_any(jmh_ctx *c, int which, const PullDst &d, void *stream) {
-    if (which != JMOUT_DEBLOCKED && which != JMOUT_RECON) return JMH_E_INVALID_ARG;
-    int r = check_pull_dst(c, d);
-    if (r) return r;
-    if (c->cur_entry < 0) return JMH_E_STATE;
-    PicBuf &b = c->ring[c->cur_entry];
-    if (which == JMOUT_DEBLOCKED && !b.deblocked) return JMH_E_STATE;
-    HCHK(hipSetDevice(c->dev));
-    hipStream_t st = (hipStream_t)stream;
-    if (!st) { if ((r = output_stream(c))) return r; st = c->ost; }
-    if (b.ev_out) HCHK(hipStreamWaitEvent(st, b.ev_out, 0));
-    else if (hipEventCreateWithFlags(&b.ev_out, hipEventDisableTiming) != hipSuccess) { b.ev_out = nullptr; return JMH_E_HIP; }
-    if ((r = pull_launch(c, d, which == JMOUT_DEBLOCKED ? b.dbk : b.rec, st))) return r;
-    HCHK(hipEventRecord(b.ev_out, st));
-    if (!stream) HCHK(hipStreamSynchronize(st));
-    return JMH_OK;
-}
-// jmh_convert_picture / jmh_convert_tensor: the host planes packed, uploaded to a scratch picture, the
-// same kernel, everything on the context's output stream and waited for
-static int convert_any(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const PullDst &d, void *stream) {
-    int r = check_pull_dst(c, d);
-    if (r) return r;
-    if (!y || !u || !v || sy < c->W || sc < c->Wc) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    if ((r = output_stream(c))) return r;
-    std::vector<uint8_t> h(c->fsize);
-    if (!pack_planes(h.data(), c->W, c->H, y, u, v, sy, sc, c->ps, c->maxv)) return JMH_E_INVALID_ARG;
-    DevTemps tmp;
-    uint8_t *src = nullptr;
-    if (tmp.alloc(&src, c->fsize) != hipSuccess) return JMH_E_OOM;
-    if (stream) HCHK(hipStreamSynchronize((hipStream_t)stream));   // the destination's last consumer
-    hipError_t e = hipMemcpyAsync(src, h.data(), c->fsize, hipMemcpyHostToDevice, c->ost);
-    if (e == hipSuccess) r = pull_launch(c, d, src, c->ost);
-    const hipError_t se = hipStreamSynchronize(c->ost);   // before src and h are freed, whatever happened
-    HCHK(e);
-    if (r) return r;
-    HCHK(se);
-    return JMH_OK;
-}
-extern "C" {
-int jmh_pull_picture(jmh_ctx *c, int which, const jmh_device_picture_out *dst) {
-    if (!c || !dst) return JMH_E_INVALID_ARG;
-    return pull_any(c, which, PullDst{dst, nullptr}, dst->stream);
-}
-int jmh_pull_tensor(jmh_ctx *c, int which, const jmh_device_tensor_out *dst) {
-    if (!c || !dst) return JMH_E_INVALID_ARG;
-    return pull_any(c, which, PullDst{nullptr, dst}, dst->stream);
-}
-int jmh_convert_picture(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const jmh_device_picture_out *dst) {
-    if (!c || !dst) return JMH_E_INVALID_ARG;
-    return convert_any(c, y, u, v, sy, sc, PullDst{dst, nullptr}, dst->stream);
-}
-int jmh_convert_tensor(jmh_ctx *c, const void *y, const void *u, const void *v, int sy, int sc, const jmh_device_tensor_out *dst) {
-    if (!c || !dst) return JMH_E_INVALID_ARG;
-    return convert_any(c, y, u, v, sy, sc, PullDst{nullptr, dst}, dst->stream);
-}
-int jmh_device_output_wait(jmh_ctx *c) {
-    if (!c) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    return output_wait(c);
-}
-int jmh_device_download(jmh_ctx *c, void *dst, const void *src, size_t n, void *stream) {
-    if (!c || !dst || !src) return JMH_E_INVALID_ARG;
-    if (!n) return JMH_OK;
-    HCHK(hipSetDevice(c->dev));
-    hipStream_t st = (hipStream_t)stream;
-    if (!st) { int r = output_stream(c); if (r) return r; st = c->ost; }
-    HCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st));
-    HCHK(hipStreamSynchronize(st));
-    return JMH_OK;
-}
-// the inverse conversion of the flags (include/jmhip_output.h): needs no context
-int jmh_yuv_coefficients(int flags, int bit_depth, int32_t out[8]) {
-    if (!out || (flags & ~JMR_FLAGS) || (bit_depth != 8 && bit_depth != 10)) return JMH_E_INVALID_ARG;
-    jmout_coef k;
-    jmout_coefficients(flags, bit_depth, &k);
-    const int32_t w[8] = {k.iy, k.irv, k.igu, k.igv, k.ibu, k.yo, k.co, k.maxv};
-    memcpy(out, w, sizeof(w));
-    return JMH_OK;
-}
-// the dequantiser of a tensor's elements on the host: needs no context
-int jmh_tensor_dequantise(int dtype, int bit_depth, const int32_t *q, size_t n, void *elems) {
-    if (dtype < 0 || dtype >= JMT_NDTYPES || (n && (!elems || !q))) return JMH_E_INVALID_ARG;
-    if (!jmt_depth_ok(dtype, bit_depth)) return JMH_E_UNSUPPORTED_CFG;
-    const int32_t M = (1 << bit_depth) - 1;
-    uint8_t *p = (uint8_t *)elems;
-    for (size_t i = 0; i < n; i++) jmout_put(p + i * jmt_es(dtype), jmt_es(dtype), jmout_dequant(dtype, jmr_clip(q[i], M), M));
-    return JMH_OK;
-}
-}  // extern "C"
-
-// the conversion of an RGB format (include/jmhip_rgb.h): needs no context
-extern "C" int jmh_rgb_coefficients(int format, int bit_depth, int32_t out[12]) {
-    if (!out || !jmr_is_rgb(format)) return JMH_E_INVALID_ARG;
-    if (!jmr_depth_ok(format, bit_depth)) return JMH_E_UNSUPPORTED_CFG;
-    jmr_coef k;
-    jmr_coefficients(format, bit_depth, &k);
-    memcpy(out, k.c, sizeof(k.c));
-    out[9] = k.yo; out[10] = k.co; out[11] = k.maxv;
-    return JMH_OK;
-}
-
 // the unit seam of the searches' spiral decode (include/jmhip_spiral.h): the device function on
 // every index of a search range
-extern "C" int jmh_spiral_positions(jmh_ctx *c, int search_range, int32_t *out_xy) {
+int jmh_spiral_positions(jmh_ctx *c, int search_range, int32_t *out_xy) {
     if (!c || !out_xy || search_range < 1 || search_range > SRMAX) return JMH_E_INVALID_ARG;
     const int side = 2 * search_range + 1, count = side * side;
     HCHK(hipSetDevice(c->dev));
@@ -2173,139 +1592,6 @@ extern "C" int jmh_spiral_positions(jmh_ctx *c, int search_range, int32_t *out_x
     return JMH_OK;
 }
 
-// ---- the unit seams, one helper each for both sample widths (pel = uint8_t: the 8-bit entries,
-//      uint16_t: the High 10 ..._u16 ones, which range-check their samples on the host) ----------
-// SetupFastFullPelSearch's SAD table.  8 bits: slot 0 against the current reference, after the
-// pictures in flight; 16 bits: the search pictures (jmh_search_pictures_u16), centres within +-SR
-template <class pel>
-static int sad_table(jmh_ctx *c, int n_mb, const int32_t *mb_xy, const int32_t *centres, uint16_t *out) {
-    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
-    if (!c || n_mb <= 0 || !mb_xy || !centres || !out) return JMH_E_INVALID_ARG;
-    for (int i = 0; i < n_mb; i++)
-        if (mb_xy[2 * i] < 0 || mb_xy[2 * i] >= c->mbw || mb_xy[2 * i + 1] < 0 || mb_xy[2 * i + 1] >= c->mbh ||
-            (wi && (abs(centres[2 * i]) > c->sr || abs(centres[2 * i + 1]) > c->sr))) return JMH_E_INVALID_ARG;
-    const pel *org, *ref;
-    if constexpr (wi) {
-        if (!c->spic[wi].cur) return JMH_E_STATE;
-        HCHK(hipSetDevice(c->dev));
-        org = (const pel *)c->spic[wi].cur; ref = (const pel *)c->spic[wi].ref;
-    } else {
-        if (c->ref_kind == REF_NONE) return JMH_E_STATE;
-        if (c->bd > 8) return JMH_E_UNSUPPORTED_CFG;   // the 8-bit SAD-table seam (High 10: jmh_ffs_sad_table_u16)
-        HCHK(hipSetDevice(c->dev));
-        int r = drain(c);
-        if (r) return r;
-        org = c->d_slots; ref = ref_ptr(c);
-    }
-    int32_t *d_xy = nullptr, *d_c = nullptr;
-    uint16_t *d_out = nullptr;
-    const size_t on = (size_t)n_mb * 16 * c->npos;
-    DevTemps tmp;
-    HCHK(tmp.alloc(&d_xy, n_mb * 8));
-    HCHK(tmp.alloc(&d_c, n_mb * 8));
-    HCHK(tmp.alloc(&d_out, on * 2));
-    HCHK(hipMemcpyAsync(d_xy, mb_xy, n_mb * 8, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpyAsync(d_c, centres, n_mb * 8, hipMemcpyHostToDevice, c->st));
-    HCHK(jmh_launch_sad_table(org, ref, c->W, c->H, c->sr, n_mb, d_xy, d_c, d_out, c->st));
-    HCHK(hipMemcpyAsync(out, d_out, on * 2, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
-}
-
-// dct_luma / dct_luma8x8 at bit_depth (EL = 16 or 64 samples per block)
-template <int EL, class pel>
-static int tq_batch(jmh_ctx *c, int n, const int16_t *resid, const pel *pred, int qp, int intra, int bit_depth, int16_t *levels, pel *recon,
-                    int32_t *coeff_cost, int32_t *nonzero) {
-    if (!c || n <= 0 || !resid || !pred || !levels || !recon || !coeff_cost || !nonzero || qp < 0 || qp > 51 || bit_depth < 8 ||
-        bit_depth > 10) return JMH_E_INVALID_ARG;
-    const int maxv = (1 << bit_depth) - 1;
-    if constexpr (sizeof(pel) == 2)
-        for (size_t k = 0; k < (size_t)n * EL; k++)   // the int32 headroom of the quantiser assumes these ranges
-            if (pred[k] > maxv || resid[k] > maxv || resid[k] < -maxv) return JMH_E_INVALID_ARG;
-    HCHK(hipSetDevice(c->dev));
-    int16_t *dr, *dl;
-    pel *dp, *drec;
-    int32_t *dcc, *dnz;
-    const size_t cb = (size_t)n * EL * 2, sb = (size_t)n * EL * sizeof(pel);   // bytes of the coefficients, of the samples
-    DevTemps tmp;
-    HCHK(tmp.alloc(&dr, cb)); HCHK(tmp.alloc(&dl, cb));
-    HCHK(tmp.alloc(&dp, sb)); HCHK(tmp.alloc(&drec, sb));
-    HCHK(tmp.alloc(&dcc, (size_t)n * 4)); HCHK(tmp.alloc(&dnz, (size_t)n * 4));
-    HCHK(hipMemcpyAsync(dr, resid, cb, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpyAsync(dp, pred, sb, hipMemcpyHostToDevice, c->st));
-    const int qpb = qp + 6 * (bit_depth - 8), qsel = q_selector(c->cfg, intra != 0);
-    if (EL == 16) HCHK(jmh_launch_tq4x4(n, dr, dp, qpb, qsel, maxv, dl, drec, dcc, dnz, c->st));
-    else HCHK(jmh_launch_tq8x8(n, dr, dp, qpb, qsel, maxv, dl, drec, dcc, dnz, c->st));
-    HCHK(hipMemcpyAsync(levels, dl, cb, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(recon, drec, sb, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(coeff_cost, dcc, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipMemcpyAsync(nonzero, dnz, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
-}
-
-// the luma pictures of the per-block searches (the 16-bit ones record their bit depth)
-template <class pel>
-static int search_pictures(jmh_ctx *c, const pel *cur_y, const pel *ref_y, int sy, int bit_depth) {
-    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
-    if (!c || !cur_y || !ref_y || sy < c->W || bit_depth < 8 || bit_depth > 10) return JMH_E_INVALID_ARG;
-    if constexpr (wi) {
-        const int maxv = (1 << bit_depth) - 1;
-        for (int y = 0; y < c->H; y++)   // out-of-range samples would break the 19-bit cost keys
-            for (int x = 0; x < c->W; x++)
-                if (cur_y[(size_t)y * sy + x] > maxv || ref_y[(size_t)y * sy + x] > maxv) return JMH_E_INVALID_ARG;
-    }
-    HCHK(hipSetDevice(c->dev));
-    auto &sp = c->spic[wi];
-    const size_t row = (size_t)c->W * sizeof(pel);
-    if (!sp.cur) {
-        if (hipMalloc(&sp.cur, row * c->H) != hipSuccess) return JMH_E_OOM;
-        if (hipMalloc(&sp.ref, row * c->H) != hipSuccess) { (void)hipFree(sp.cur); sp.cur = nullptr; return JMH_E_OOM; }
-    }
-    HCHK(hipStreamSynchronize(c->st));   // an earlier search may still read the buffers
-    HCHK(hipMemcpy2DAsync(sp.cur, row, cur_y, (size_t)sy * sizeof(pel), row, c->H, hipMemcpyHostToDevice, c->st));
-    HCHK(hipMemcpy2DAsync(sp.ref, row, ref_y, (size_t)sy * sizeof(pel), row, c->H, hipMemcpyHostToDevice, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    if (wi) c->hbd_bits = bit_depth;
-    return JMH_OK;
-}
-
-static int check_block_requests(const jmh_ctx *c, int n, const jmh_block_search *req) {
-    for (int i = 0; i < n; i++) {   // the kernel's block and window assumptions, checked on the host
-        const jmh_block_search &q = req[i];
-        if (q.blocktype < 1 || q.blocktype > 7 || q.mb_x < 0 || q.mb_x >= c->mbw || q.mb_y < 0 || q.mb_y >= c->mbh) return JMH_E_INVALID_ARG;
-        static const int bw4[8] = {4, 4, 4, 2, 2, 2, 1, 1}, bh4[8] = {4, 4, 2, 4, 2, 1, 2, 1};
-        if (q.block_x < 0 || q.block_y < 0 || q.block_x + bw4[q.blocktype] > 4 || q.block_y + bh4[q.blocktype] > 4) return JMH_E_INVALID_ARG;
-        if (q.search_range < 0 || q.search_range > c->sr) return JMH_E_INVALID_ARG;
-        if (q.search_range > SRMAX) return JMH_E_UNSUPPORTED_CFG;   // 13-bit spiral order keys: (2 SR + 1)^2 < 8192
-        if (q.lambda_factor < 0 || q.lambda_factor > (1 << 24)) return JMH_E_INVALID_ARG;
-        if (q.search_mode != 0 && q.search_mode != -1) return JMH_E_UNSUPPORTED_CFG;
-        if (abs(q.centre[0]) > 2048 || abs(q.centre[1]) > 2048 || abs(q.pred_mv[0]) > 8192 || abs(q.pred_mv[1]) > 8192) return JMH_E_INVALID_ARG;
-    }
-    return JMH_OK;
-}
-// BlockMotionSearch per request on the search pictures of pel's width; maxv = 2^(their bit depth) - 1
-template <class pel>
-static int block_motion_search(jmh_ctx *c, int n, const jmh_block_search *req, jmh_block_result *res, int maxv) {
-    if (!c || n <= 0 || !req || !res) return JMH_E_INVALID_ARG;
-    constexpr int wi = sizeof(pel) == 2;   // index of the sample width (spic)
-    const auto &sp = c->spic[wi];
-    if (!sp.cur) return JMH_E_STATE;
-    int r = check_block_requests(c, n, req);
-    if (r) return r;
-    HCHK(hipSetDevice(c->dev));
-    DevTemps tmp;
-    jmh_block_search *d_req;
-    jmh_block_result *d_res;
-    HCHK(tmp.alloc(&d_req, (size_t)n * sizeof(jmh_block_search)));
-    HCHK(tmp.alloc(&d_res, (size_t)n * sizeof(jmh_block_result)));
-    HCHK(hipMemcpyAsync(d_req, req, (size_t)n * sizeof(jmh_block_search), hipMemcpyHostToDevice, c->st));
-    HCHK(jmh_launch_block_search(n, d_req, d_res, (const pel *)sp.cur, (const pel *)sp.ref, c->W, c->H, c->cfg.use_hadamard, maxv, c->st));
-    HCHK(hipMemcpyAsync(res, d_res, (size_t)n * sizeof(jmh_block_result), hipMemcpyDeviceToHost, c->st));
-    HCHK(hipStreamSynchronize(c->st));
-    return JMH_OK;
-}
-extern "C" {
 int jmh_read_recon(jmh_ctx *c, uint8_t *y, uint8_t *u, uint8_t *v, int sy, int sc) { return read_pic(c, y, u, v, sy, sc, false, false); }
 int jmh_read_recon_u16(jmh_ctx *c, uint16_t *y, uint16_t *u, uint16_t *v, int sy, int sc) { return read_pic(c, y, u, v, sy, sc, true, false); }
 int jmh_read_deblocked(jmh_ctx *c, uint8_t *y, uint8_t *u, uint8_t *v, int sy, int sc) { return read_pic(c, y, u, v, sy, sc, false, true); }

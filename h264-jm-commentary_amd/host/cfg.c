@@ -200,15 +200,6 @@ static int parse_file(jm_input *inp, const char *fn, char *err, int errlen) {
 static jm_device_push_fn device_input_fn;
 void jm_set_device_input(jm_device_push_fn fn) { device_input_fn = fn; }
 jm_device_push_fn jm_device_input(void) { return device_input_fn; }
-static jm_device_push_rgb_fn device_input_rgb_fn;
-void jm_set_device_input_rgb(jm_device_push_rgb_fn fn) { device_input_rgb_fn = fn; }
-jm_device_push_rgb_fn jm_device_input_rgb(void) { return device_input_rgb_fn; }
-static jm_device_push_tensor_fn device_input_tensor_fn;
-void jm_set_device_input_tensor(jm_device_push_tensor_fn fn) { device_input_tensor_fn = fn; }
-jm_device_push_tensor_fn jm_device_input_tensor(void) { return device_input_tensor_fn; }
-static jm_device_push_rgb_fn device_input_yuv_fn;
-void jm_set_device_input_yuv(jm_device_push_rgb_fn fn) { device_input_yuv_fn = fn; }
-jm_device_push_rgb_fn jm_device_input_yuv(void) { return device_input_yuv_fn; }
 static jm_device_scale_fn device_input_scale_fn;
 void jm_set_device_input_scale(jm_device_scale_fn fn) { device_input_scale_fn = fn; }
 jm_device_scale_fn jm_device_input_scale(void) { return device_input_scale_fn; }
@@ -233,13 +224,13 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->device_input_format && !inp->device_input) { snprintf(err, errlen, "DeviceInputFormat=%d names the layout of a picture pushed from device memory: it needs DeviceInput=1", inp->device_input_format); return -1; }
     if (inp->device_input_format && inp->device_input_format < 16) { snprintf(err, errlen, "DeviceInputFormat=%d not supported (0: YUV, 16 BGRA8, 17 RGBA8, 18 RGB10A2, 19 BGR10A2)", inp->device_input_format); return -1; }
     if ((inp->device_input_matrix || inp->device_input_full) && !inp->device_input_format && !inp->device_input_tensor) { snprintf(err, errlen, "DeviceInputMatrix / DeviceInputFullRange describe an RGB source: they need DeviceInput=1 and DeviceInputFormat=16..19"); return -1; }
-    if (inp->device_input_format && !device_input_rgb_fn) { snprintf(err, errlen, "DeviceInputFormat=%d converts the source on the device: it needs the device backend (this build has no RGB device input: DeviceInputFormat=0)", inp->device_input_format); return -1; }
+    if (inp->device_input_format && !device_input_fn) { snprintf(err, errlen, "DeviceInputFormat=%d converts the source on the device: it needs the device backend (this build has no RGB device input: DeviceInputFormat=0)", inp->device_input_format); return -1; }
     if (inp->device_input_format && inp->bit_depth_luma != (inp->device_input_format >= 18 ? 10 : 8)) { snprintf(err, errlen, "DeviceInputFormat=%d holds %d-bit components: it needs SourceBitDepthLuma=%d (got %d)", inp->device_input_format, inp->device_input_format >= 18 ? 10 : 8, inp->device_input_format >= 18 ? 10 : 8, inp->bit_depth_luma); return -1; }
     if (inp->device_input_format && !strncmp(inp->infile, "synthetic:", 10)) { snprintf(err, errlen, "DeviceInputFormat=%d reads RGB frames from InputFile: the synthetic source is YUV (InputFile=%s)", inp->device_input_format, inp->infile); return -1; }
     if (inp->device_input_format && !inp->device_writer_async) { snprintf(err, errlen, "DeviceInputFormat=%d leaves no YUV source on the host, so the distortion comes from the device's SSDs: it needs DeviceWriterAsync=1 (and so DeviceCAVLC=1 or DeviceCABAC=1)", inp->device_input_format); return -1; }
     if (inp->device_input_tensor && !inp->device_input) { snprintf(err, errlen, "DeviceInputTensor=%d names the layout of a tensor pushed from device memory: it needs DeviceInput=1", inp->device_input_tensor); return -1; }
     if (inp->device_input_tensor && inp->device_input_format) { snprintf(err, errlen, "DeviceInputTensor=%d and DeviceInputFormat=%d both name the layout of InputFile: set one of them", inp->device_input_tensor, inp->device_input_format); return -1; }
-    if (inp->device_input_tensor && !device_input_tensor_fn) { snprintf(err, errlen, "DeviceInputTensor=%d quantises and converts the source on the device: it needs the device backend (this build has no tensor device input: DeviceInputTensor=0)", inp->device_input_tensor); return -1; }
+    if (inp->device_input_tensor && !device_input_fn) { snprintf(err, errlen, "DeviceInputTensor=%d quantises and converts the source on the device: it needs the device backend (this build has no tensor device input: DeviceInputTensor=0)", inp->device_input_tensor); return -1; }
     if (inp->device_input_tensor && inp->device_input_tensor < 3 && inp->bit_depth_luma != 8) { snprintf(err, errlen, "DeviceInputTensor=%d holds 8-bit components: it needs SourceBitDepthLuma=8 (got %d)", inp->device_input_tensor, inp->bit_depth_luma); return -1; }
     if (inp->device_input_tensor == 3 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputTensor=3 (gbrp10le) holds 10-bit components: it needs SourceBitDepthLuma=10 (got %d)", inp->bit_depth_luma); return -1; }
     if (inp->device_input_tensor == 4 && inp->bit_depth_luma != 8 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputTensor=4 (gbrpf32le) is quantised to 8 or 10 bits: it needs SourceBitDepthLuma=8 or 10 (got %d)", inp->bit_depth_luma); return -1; }
@@ -249,7 +240,7 @@ int jm_patch_input(jm_input *inp, char *err, int errlen) {
     if (inp->device_input_yuv && !jm_yuv_format_ok(inp->device_input_yuv)) { snprintf(err, errlen, "DeviceInputYUV=%d not supported (0: 4:2:0, 32 I422, 33 NV16, 34 YUYV, 35 UYVY, 36 I444, 37 VUYA8, 40 I210, 41 P210, 42 Y210, 43 I410, 44 Y410)", inp->device_input_yuv); return -1; }
     if (inp->device_input_yuv && inp->device_input_format) { snprintf(err, errlen, "DeviceInputYUV=%d and DeviceInputFormat=%d both name the layout of InputFile: set one of them", inp->device_input_yuv, inp->device_input_format); return -1; }
     if (inp->device_input_yuv && inp->device_input_tensor) { snprintf(err, errlen, "DeviceInputYUV=%d and DeviceInputTensor=%d both name the layout of InputFile: set one of them", inp->device_input_yuv, inp->device_input_tensor); return -1; }
-    if (inp->device_input_yuv && !device_input_yuv_fn) { snprintf(err, errlen, "DeviceInputYUV=%d reduces the source to 4:2:0 on the device: it needs the device backend (this build has no 4:2:2 / 4:4:4 device input: DeviceInputYUV=0)", inp->device_input_yuv); return -1; }
+    if (inp->device_input_yuv && !device_input_fn) { snprintf(err, errlen, "DeviceInputYUV=%d reduces the source to 4:2:0 on the device: it needs the device backend (this build has no 4:2:2 / 4:4:4 device input: DeviceInputYUV=0)", inp->device_input_yuv); return -1; }
     if (inp->device_input_yuv && inp->device_input_yuv < 40 && inp->bit_depth_luma != 8) { snprintf(err, errlen, "DeviceInputYUV=%d holds 8-bit samples: it needs SourceBitDepthLuma=8 (got %d)", inp->device_input_yuv, inp->bit_depth_luma); return -1; }
     if ((inp->device_input_yuv == 40 || inp->device_input_yuv == 43) && inp->bit_depth_luma != 9 && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputYUV=%d holds 9- or 10-bit samples in 16-bit words: it needs SourceBitDepthLuma=9 or 10 (got %d)", inp->device_input_yuv, inp->bit_depth_luma); return -1; }
     if ((inp->device_input_yuv == 41 || inp->device_input_yuv == 42 || inp->device_input_yuv == 44) && inp->bit_depth_luma != 10) { snprintf(err, errlen, "DeviceInputYUV=%d holds 10-bit samples: it needs SourceBitDepthLuma=10 (got %d)", inp->device_input_yuv, inp->bit_depth_luma); return -1; }

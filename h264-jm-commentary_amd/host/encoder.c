@@ -433,38 +433,33 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         fprintf(stderr, "DeviceInput=1 needs the device backend (backend '%s' has no device input: DeviceInput=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
     }
-    const int rgb_format = inp->device_input_format ? inp->device_input_format | (inp->device_input_matrix ? JMH_PIX_BT709 : 0) |
-                                                          (inp->device_input_full ? JMH_PIX_FULL_RANGE : 0) : 0;
-    const jm_device_push_rgb_fn device_input_rgb_fn = rgb_format ? jm_device_input_rgb() : NULL;
-    if (rgb_format && (!device_input_fn || !device_input_rgb_fn)) {
-        fprintf(stderr, "DeviceInputFormat=%d needs DeviceInput=1 on the device backend (backend '%s' has no RGB device input: DeviceInputFormat=0)\n",
-                inp->device_input_format, be->name);
-        return JMH_E_UNSUPPORTED_CFG;
-    }
-    if (rgb_format && !inp->device_writer_async) {
-        fprintf(stderr, "DeviceInputFormat=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n", inp->device_input_format);
-        return JMH_E_UNSUPPORTED_CFG;
-    }
-    const int tensor_kind = inp->device_input_tensor;
-    const int tensor_flags = (inp->device_input_matrix ? JMH_PIX_BT709 : 0) | (inp->device_input_full ? JMH_PIX_FULL_RANGE : 0);
-    const jm_device_push_tensor_fn device_input_tensor_fn = tensor_kind ? jm_device_input_tensor() : NULL;
-    if (tensor_kind && (rgb_format || !device_input_fn || !device_input_tensor_fn)) {
-        fprintf(stderr, "DeviceInputTensor=%d needs DeviceInput=1 on the device backend and DeviceInputFormat=0 (backend '%s')\n", tensor_kind, be->name);
-        return JMH_E_UNSUPPORTED_CFG;
-    }
-    if (tensor_kind && !inp->device_writer_async) {
-        fprintf(stderr, "DeviceInputTensor=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n", tensor_kind);
-        return JMH_E_UNSUPPORTED_CFG;
-    }
-    const int yuv_format = inp->device_input_yuv ? inp->device_input_yuv | (inp->device_input_chroma_left && jm_yuv_is444(inp->device_input_yuv) ? JMH_PIX_CHROMA_LEFT : 0) : 0;
-    const jm_device_push_rgb_fn device_input_yuv_fn = yuv_format ? jm_device_input_yuv() : NULL;
-    if (yuv_format && (rgb_format || tensor_kind || !device_input_fn || !device_input_yuv_fn)) {
-        fprintf(stderr, "DeviceInputYUV=%d needs DeviceInput=1 on the device backend, DeviceInputFormat=0 and DeviceInputTensor=0 (backend '%s')\n", inp->device_input_yuv, be->name);
-        return JMH_E_UNSUPPORTED_CFG;
-    }
-    if (yuv_format && !inp->device_writer_async) {
-        fprintf(stderr, "DeviceInputYUV=%d needs DeviceWriterAsync=1 (no 4:2:0 source on the host: the distortion is the device's)\n", inp->device_input_yuv);
-        return JMH_E_UNSUPPORTED_CFG;
+    /* the source the backend pushes: 4:2:0 planes under DeviceInput alone, else the layout its key names.  The keys in
+       the order they are checked, each with its value, the source's code and flags and its refusals: without DeviceInput
+       on the device backend or beside a key before it, without DeviceWriterAsync, with the synthetic source */
+    const int rgb_flags = (inp->device_input_matrix ? JMH_PIX_BT709 : 0) | (inp->device_input_full ? JMH_PIX_FULL_RANGE : 0);
+    const struct { int val, kind, code, flags; const char *needs, *async, *synthetic; } src_keys[3] = {
+        {inp->device_input_format, JM_SRC_RGB, inp->device_input_format | rgb_flags, 0,
+         "DeviceInputFormat=%d needs DeviceInput=1 on the device backend (backend '%s' has no RGB device input: DeviceInputFormat=0)\n",
+         "DeviceInputFormat=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n",
+         "DeviceInputFormat=%d reads RGB frames from InputFile: the synthetic source is YUV\n"},
+        {inp->device_input_tensor, JM_SRC_TENSOR, inp->device_input_tensor, rgb_flags,
+         "DeviceInputTensor=%d needs DeviceInput=1 on the device backend and DeviceInputFormat=0 (backend '%s')\n",
+         "DeviceInputTensor=%d needs DeviceWriterAsync=1 (no YUV source on the host: the distortion is the device's)\n",
+         "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV\n"},
+        {inp->device_input_yuv, JM_SRC_YUV,
+         inp->device_input_yuv | (inp->device_input_chroma_left && jm_yuv_is444(inp->device_input_yuv) ? JMH_PIX_CHROMA_LEFT : 0), 0,
+         "DeviceInputYUV=%d needs DeviceInput=1 on the device backend, DeviceInputFormat=0 and DeviceInputTensor=0 (backend '%s')\n",
+         "DeviceInputYUV=%d needs DeviceWriterAsync=1 (no 4:2:0 source on the host: the distortion is the device's)\n",
+         "DeviceInputYUV=%d reads 4:2:2 or 4:4:4 frames from InputFile: the synthetic source is 4:2:0\n"},
+    };
+    jm_device_source src = {JM_SRC_PLANES, 0, 0, NULL, NULL, 0, 0};
+    int src_key = -1;                            /* the key that names the layout of InputFile, if one does */
+    for (int k = 0; k < 3; k++) {
+        if (!src_keys[k].val) continue;
+        if (src_key >= 0 || !device_input_fn) { fprintf(stderr, src_keys[k].needs, src_keys[k].val, be->name); return JMH_E_UNSUPPORTED_CFG; }
+        if (!inp->device_writer_async) { fprintf(stderr, src_keys[k].async, src_keys[k].val); return JMH_E_UNSUPPORTED_CFG; }
+        src.kind = src_keys[k].kind; src.code = src_keys[k].code; src.flags = src_keys[k].flags;
+        src_key = k;
     }
     const int scale = inp->device_input_scale;
     const jm_device_scale_fn device_scale_fn = scale ? jm_device_input_scale() : NULL;
@@ -474,6 +469,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     }
     /* the frames of InputFile: DeviceInputWidth x DeviceInputHeight under DeviceInputScale, else the display size */
     const int src_w = scale ? inp->device_input_width : inp->width, src_h = scale ? inp->device_input_height : inp->height;
+    src.w = src_w; src.h = src_h;
     if (inp->device_writer_async && !(device_coded_push_fn && device_coded_pop_fn)) {
         fprintf(stderr, "DeviceWriterAsync=1 needs the device backend (backend '%s' has no coded push / pop: DeviceWriterAsync=0)\n", be->name);
         return JMH_E_UNSUPPORTED_CFG;
@@ -503,9 +499,7 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     FILE *fin = NULL, *fout = NULL, *frec = NULL;
     uint64_t seed = 0;
     int synthetic = !strncmp(inp->infile, "synthetic:", 10);
-    if (synthetic && rgb_format) { fprintf(stderr, "DeviceInputFormat=%d reads RGB frames from InputFile: the synthetic source is YUV\n", inp->device_input_format); return JMH_E_UNSUPPORTED_CFG; }
-    if (synthetic && tensor_kind) { fprintf(stderr, "DeviceInputTensor=%d reads RGB frames from InputFile: the synthetic source is YUV\n", tensor_kind); return JMH_E_UNSUPPORTED_CFG; }
-    if (synthetic && yuv_format) { fprintf(stderr, "DeviceInputYUV=%d reads 4:2:2 or 4:4:4 frames from InputFile: the synthetic source is 4:2:0\n", inp->device_input_yuv); return JMH_E_UNSUPPORTED_CFG; }
+    if (synthetic && src_key >= 0) { fprintf(stderr, src_keys[src_key].synthetic, src_keys[src_key].val); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic && scale) { fprintf(stderr, "DeviceInputScale=%d reads frames of DeviceInputWidth x DeviceInputHeight from InputFile: the synthetic source has the coded size\n", scale); return JMH_E_UNSUPPORTED_CFG; }
     if (synthetic) seed = strtoull(inp->infile + 10, NULL, 10);
     else if (!(fin = fopen(inp->infile, "rb"))) { fprintf(stderr, "Input file %s does not exist\n", inp->infile); return JMH_E_INVALID_ARG; }
@@ -560,10 +554,10 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
     memset(&rec, 0, sizeof(rec));
     /* DeviceInputFormat: one frame as read, height rows of 4 * width bytes (free again when its upload returns);
        DeviceInputTensor: one frame of its file, in the same buffer; DeviceInputYUV: one frame of its layout, likewise */
-    const int raw_source = rgb_format || tensor_kind || yuv_format;
-    const size_t rgb_bytes = tensor_kind ? jm_tensor_frame_bytes(tensor_kind, src_w, src_h)
-                           : yuv_format ? jm_yuv_frame_bytes(inp->device_input_yuv, src_w, src_h) : (size_t)4 * src_w * src_h;
+    const int raw_source = src.kind != JM_SRC_PLANES;
+    const size_t rgb_bytes = jm_source_frame_bytes(&src);
     uint8_t *rgb = raw_source ? (uint8_t *)malloc(rgb_bytes) : NULL;
+    src.frame = rgb;
     /* DeviceInputScale with a YUV file: one frame as read, at its own size (free again when its upload returns) */
     jm_pic big;
     memset(&big, 0, sizeof(big));
@@ -642,16 +636,16 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             fprintf(log, " (CABAC slice data written on the device, every slice in chunks of %d bins: no writer threads, no per-macroblock rate check)\n",
                     inp->device_cabac_split);
         else if (inp->device_cabac) fprintf(log, " (CABAC slice data written on the device: no writer threads, no per-macroblock rate check)\n");
-        if (rgb_format)
+        if (src.kind == JM_SRC_RGB)
             fprintf(log, " (the source is RGB, format %d: converted on the device with the BT.%s matrix at %s range; the stream does not signal either)\n",
                     inp->device_input_format, inp->device_input_matrix ? "709" : "601", inp->device_input_full ? "full" : "limited");
-        if (tensor_kind)
+        if (src.kind == JM_SRC_TENSOR)
             fprintf(log, " (the source is an RGB tensor, %s: quantised and converted on the device with the BT.%s matrix at %s range; the stream does not signal either)\n",
-                    tensor_kind == 1 ? "rgb24" : tensor_kind == 2 ? "gbrp" : tensor_kind == 3 ? "gbrp10le" : "gbrpf32le",
+                    src.code == 1 ? "rgb24" : src.code == 2 ? "gbrp" : src.code == 3 ? "gbrp10le" : "gbrpf32le",
                     inp->device_input_matrix ? "709" : "601", inp->device_input_full ? "full" : "limited");
-        if (yuv_format)
+        if (src.kind == JM_SRC_YUV)
             fprintf(log, " (the source is %s, format %d: its chroma is reduced to 4:2:0 on the device%s)\n", jm_yuv_is444(inp->device_input_yuv) ? "4:4:4" : "4:2:2",
-                    inp->device_input_yuv, yuv_format & JMH_PIX_CHROMA_LEFT ? ", left-sited" : "");
+                    inp->device_input_yuv, src.code & JMH_PIX_CHROMA_LEFT ? ", left-sited" : "");
         if (drec.fn)
             fprintf(log, " (ReconFile holds %s %s: the display-size picture converted on the device with the BT.%s matrix at %s range and downloaded)\n",
                     drec.tensor ? "an RGB tensor," : "RGB, format",
@@ -821,11 +815,12 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
         int idx = inp->start_frame + f;
         double tr = now_ms();
         if (raw_source) {
-            if (fseek(fin, (long)rgb_bytes * idx, SEEK_SET) || fread(rgb, 1, rgb_bytes, fin) != rgb_bytes) { fprintf(stderr, "ReadOneFrame: cannot read %s frame %d\n", yuv_format ? "YUV" : "RGB", idx); st_ret = JMH_E_INVALID_ARG; break; }
+            if (fseek(fin, (long)rgb_bytes * idx, SEEK_SET) || fread(rgb, 1, rgb_bytes, fin) != rgb_bytes) { fprintf(stderr, "ReadOneFrame: cannot read %s frame %d\n", src.kind == JM_SRC_YUV ? "YUV" : "RGB", idx); st_ret = JMH_E_INVALID_ARG; break; }
         } else
         if (synthetic) jm_synth_frame(&p->cur, inp->width, inp->height, seed, idx);
         else if (jm_read_yuv_frame(fin, scale ? &big : &p->cur, src_w, src_h, idx)) { fprintf(stderr, "ReadOneFrame: cannot read frame %d\n", idx); st_ret = JMH_E_INVALID_ARG; break; }
         read_ms += now_ms() - tr;
+        src.pic = raw_source ? NULL : scale ? &big : &p->cur;   /* 4:2:0 planes: the picture just read */
         p->f = f;
         p->is_i = f == 0 || (inp->intra_period && f % inp->intra_period == 0);
         p->frame_num = frame_num++;
@@ -851,13 +846,10 @@ int jm_encode_sequence(const jm_input *inp, jm_backend *be, jm_stats *st, FILE *
             PEND_SLICE(p, sl);
             device_slice_headers(d, &s, &sl);
             if (nal && !(r = device_slice_heads(d, &sl))) r = device_nal_fn(be->ctx, d->n, d->nh);
-            if (!r) r = tensor_kind ? device_input_tensor_fn(be->ctx, rgb, tensor_kind, tensor_flags, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
-                  : rgb_format ? device_input_rgb_fn(be->ctx, rgb, rgb_format, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
-                  : yuv_format ? device_input_yuv_fn(be->ctx, rgb, yuv_format, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
-                  : device_input_fn ? device_input_fn(be->ctx, scale ? &big : &p->cur, src_w, src_h, fp, d->n, d->cs, inp->width, inp->height)
-                                : device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
+            if (!r) r = device_input_fn ? device_input_fn(be->ctx, &src, fp, d->n, d->cs, inp->width, inp->height)
+                                        : device_coded_push_fn(be->ctx, &p->cur, fp, d->n, d->cs, inp->width, inp->height);
         } else
-        if (!r) r = device_input_fn ? device_input_fn(be->ctx, &p->cur, inp->width, inp->height, fp, 0, NULL, 0, 0)
+        if (!r) r = device_input_fn ? device_input_fn(be->ctx, &src, fp, 0, NULL, 0, 0)
                   : pipelined ? be->push(be->ctx, &p->cur, fp) : be->encode_frame(be->ctx, &p->cur, fp);
         double met = now_ms() - t0;
         if (r) { fprintf(stderr, "hot path backend '%s' failed: status %d\n", be->name, r); st_ret = r; break; }

@@ -300,25 +300,6 @@ void jm_set_device_coded(jm_coded_push_fn push, jm_coded_pop_fn pop);
    include/jmhip_nal.h); unset on a backend without it, where the key is rejected */
 typedef int (*jm_nal_heads_fn)(void *ctx, int n, const jmh_nal_head *heads);
 void jm_set_device_nal(jm_nal_heads_fn fn);
-/* DeviceInput 1: the backend's push of a picture from device memory (jmh_frame_push_device; with n
-   slices jmh_frame_push_coded_device, include/jmhip_input.h).  cur holds disp_w x disp_h samples at
-   the coded picture's strides, unpadded.  Registered before jm_configure: PatchInp rejects the key
-   on a backend without one */
-typedef int (*jm_device_push_fn)(void *ctx, const jm_pic *cur, int disp_w, int disp_h, const jmh_frame_params *fp, int n,
-                                 const jmh_coded_slice *slices, int crop_w, int crop_h);
-void jm_set_device_input(jm_device_push_fn fn);
-jm_device_push_fn jm_device_input(void);
-/* DeviceInputFormat 16..19: the backend's push of an RGB picture (jmh_frame_push_coded_device with a
-   format of include/jmhip_rgb.h, flags included).  rgb holds disp_h rows of 4 * disp_w bytes */
-typedef int (*jm_device_push_rgb_fn)(void *ctx, const void *rgb, int format, int disp_w, int disp_h, const jmh_frame_params *fp, int n,
-                                     const jmh_coded_slice *slices, int crop_w, int crop_h);
-void jm_set_device_input_rgb(jm_device_push_rgb_fn fn);
-jm_device_push_rgb_fn jm_device_input_rgb(void);
-/* DeviceInputYUV 32..37, 40..44: the backend's push of a 4:2:2 or 4:4:4 picture (jmh_frame_push_coded_device with a
-   format of include/jmhip_yuv.h, its flag included).  frame holds jm_yuv_frame_bytes(format, disp_w, disp_h) bytes
-   as read: the layout's planes one after the other, every row tight */
-void jm_set_device_input_yuv(jm_device_push_rgb_fn fn);
-jm_device_push_rgb_fn jm_device_input_yuv(void);
 /* the layouts of a DeviceInputYUV file: whether the key names one, whether it is 4:4:4, the bytes of a row of its
    plane sp (0 for a plane the layout has not) and of a frame (every plane has h rows) */
 static inline int jm_yuv_format_ok(int f) { return (f >= 32 && f <= 37) || (f >= 40 && f <= 44); }
@@ -337,12 +318,6 @@ static inline size_t jm_yuv_row_bytes(int f, int sp, int w) {
 static inline size_t jm_yuv_frame_bytes(int f, int w, int h) {
     return (jm_yuv_row_bytes(f, 0, w) + jm_yuv_row_bytes(f, 1, w) + jm_yuv_row_bytes(f, 2, w)) * (size_t)h;
 }
-/* DeviceInputTensor 1..4: the backend's push of a frame as a device tensor (jmh_frame_push_coded_tensor).
-   frame holds jm_tensor_frame_bytes(kind, disp_w, disp_h) bytes as read; flags: JMH_PIX_BT709 | JMH_PIX_FULL_RANGE */
-typedef int (*jm_device_push_tensor_fn)(void *ctx, const void *frame, int kind, int flags, int disp_w, int disp_h, const jmh_frame_params *fp,
-                                        int n, const jmh_coded_slice *slices, int crop_w, int crop_h);
-void jm_set_device_input_tensor(jm_device_push_tensor_fn fn);
-jm_device_push_tensor_fn jm_device_input_tensor(void);
 /* DeviceInputScale 1..3: the backend's sticky scale of its device pushes (jmh_input_scale, include/jmhip_scale.h):
    every push that follows takes a source of any even size and resamples it to out_w x out_h.  Registered before
    jm_configure: PatchInp rejects the keys on a backend without one */
@@ -361,6 +336,32 @@ static inline int jm_tensor_elem_bytes(int kind) { return kind == 4 ? 4 : kind =
 static inline size_t jm_tensor_frame_bytes(int kind, int w, int h) { return (size_t)3 * jm_tensor_elem_bytes(kind) * w * h; }
 /* bytes of a frame of a ReconFile written with DeviceReconFormat (tensor 0) or DeviceReconTensor */
 static inline size_t jm_recon_frame_bytes(int tensor, int w, int h) { return tensor ? jm_tensor_frame_bytes(tensor, w, h) : (size_t)4 * w * h; }
+/* DeviceInput 1: one frame of InputFile as the backend pushes it from device memory.
+   JM_SRC_PLANES  pic holds w x h samples of 4:2:0 planes at the coded picture's strides, unpadded (DeviceInput alone)
+   JM_SRC_RGB     frame holds h rows of 4 * w bytes; code: a format of include/jmhip_rgb.h, flags included (DeviceInputFormat 16..19)
+   JM_SRC_YUV     frame holds the layout's planes one after the other, every row tight; code: a format of include/jmhip_yuv.h,
+                  its flag included (DeviceInputYUV 32..37, 40..44)
+   JM_SRC_TENSOR  frame holds rgb24, gbrp, gbrp10le or gbrpf32le; code: DeviceInputTensor 1..4, flags: JMH_PIX_BT709 |
+                  JMH_PIX_FULL_RANGE */
+enum { JM_SRC_PLANES, JM_SRC_RGB, JM_SRC_YUV, JM_SRC_TENSOR };
+typedef struct {
+    int kind, code, flags;
+    const jm_pic *pic;
+    const void *frame;
+    int w, h;
+} jm_device_source;
+/* bytes of the frame of a source other than JM_SRC_PLANES */
+static inline size_t jm_source_frame_bytes(const jm_device_source *s) {
+    return s->kind == JM_SRC_TENSOR ? jm_tensor_frame_bytes(s->code, s->w, s->h)
+           : s->kind == JM_SRC_YUV  ? jm_yuv_frame_bytes(s->code & ~JMH_PIX_CHROMA_LEFT, s->w, s->h) : (size_t)4 * s->w * s->h;
+}
+/* the backend's push of a source (jmh_frame_push_device, jmh_frame_push_coded_device, jmh_frame_push_coded_tensor:
+   include/jmhip_input.h, jmhip_tensor.h): with n slices a coded push; n 0, JM_SRC_PLANES only, an ordinary one.
+   Registered before jm_configure: PatchInp rejects the DeviceInput keys on a backend without one */
+typedef int (*jm_device_push_fn)(void *ctx, const jm_device_source *src, const jmh_frame_params *fp, int n, const jmh_coded_slice *slices,
+                                 int crop_w, int crop_h);
+void jm_set_device_input(jm_device_push_fn fn);
+jm_device_push_fn jm_device_input(void);
 /* 10 log10(peak^2 w h / ssd) with psnr_pl's arithmetic (99.0 at ssd 0): the PSNR of a w x h plane of
    bit_depth-bit samples from its summed squared error */
 double jm_psnr_from_ssd(uint64_t ssd, int w, int h, int bit_depth);

@@ -58,104 +58,72 @@ static int gpu_nal_heads(void *ctx, int n, const jmh_nal_head *heads) { return j
 static int gpu_pop_coded(void *ctx, uint8_t *out, size_t cap, jmh_coded_bytes *where, jmh_coded_stats *stats) {
     return jmh_frame_pop_coded((jmh_ctx *)ctx, out, cap, where, stats);
 }
-/* DeviceInput 1: the picture as read (display size, the coded picture's strides, unpadded) uploaded
-   raw into one device buffer and pushed from there.  The upload and the push share a stream of the
-   caller's, so the next picture's upload follows this picture's packing kernel. */
+/* a frame of a tensor file (DeviceInputTensor / DeviceReconTensor 1..4) as a device tensor: the offsets of R, G, B,
+   the strides, the element type.  rgb24 (1): pixels of R, G, B; gbrp, gbrp10le, gbrpf32le (2..4): planes G, B, R */
+typedef struct { size_t off[3]; int64_t stride_x, stride_y; int dtype; } gpu_tensor_layout;
+static gpu_tensor_layout gpu_tensor_frame(int kind, int dw, int dh) {
+    const size_t es = (size_t)jm_tensor_elem_bytes(kind), plane = es * dw * dh;
+    const gpu_tensor_layout packed = {{0, 1, 2}, 3, (int64_t)3 * dw, JMH_T_U8};
+    const gpu_tensor_layout planar = {{2 * plane, 0, plane}, (int64_t)es, (int64_t)es * dw, kind == 4 ? JMH_T_F32 : kind == 3 ? JMH_T_U16 : JMH_T_U8};
+    return kind == 1 ? packed : planar;
+}
+/* DeviceInput 1: the frame as read uploaded raw into one device buffer and pushed from there.  The upload and the
+   push share a stream of the caller's, so the next picture's upload follows this picture's packing kernel. */
 static struct { void *buf, *stream; size_t bytes; } gpu_in;
-static int gpu_push_device(void *ctx, const jm_pic *cur, int dw, int dh, const jmh_frame_params *fp, int n, const jmh_coded_slice *sl, int cw,
-                           int ch) {
-    const size_t ps = cur->bd > 8 ? 2 : 1, luma = (size_t)cur->w * cur->h * ps, bytes = luma * 3 / 2;
+static int gpu_in_upload(void *ctx, size_t bytes, const void *data) {
     int r;
     if (!gpu_in.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_in.stream))) return r;
     if (gpu_in.bytes < bytes) {
         if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_in.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_in.buf))) return r;
         gpu_in.bytes = bytes;
     }
-    if ((r = jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, cur->bd > 8 ? (const void *)cur->Y : (const void *)cur->y, bytes, gpu_in.stream))) return r;
-    jmh_device_picture pic;
-    memset(&pic, 0, sizeof(pic));
-    pic.format = cur->bd > 8 ? JMH_PIX_I010 : JMH_PIX_I420;
-    pic.width = dw; pic.height = dh;
-    pic.plane[0] = gpu_in.buf;
-    pic.plane[1] = (const uint8_t *)gpu_in.buf + luma;
-    pic.plane[2] = (const uint8_t *)gpu_in.buf + luma + luma / 4;
-    pic.stride[0] = (int64_t)cur->w * ps; pic.stride[1] = pic.stride[2] = (int64_t)(cur->w / 2) * ps;
-    pic.stream = gpu_in.stream;
-    return n ? jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch) : jmh_frame_push_device((jmh_ctx *)ctx, &pic, fp);
+    return jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, data, bytes, gpu_in.stream);
 }
-/* DeviceInputFormat 16..19: the RGB frame as read, through the same buffer and stream; the device converts it */
-static int gpu_push_device_rgb(void *ctx, const void *rgb, int format, int dw, int dh, const jmh_frame_params *fp, int n, const jmh_coded_slice *sl,
-                               int cw, int ch) {
-    const size_t bytes = (size_t)4 * dw * dh;
+/* the source described as the library takes it: 4:2:0 planes (display size, the coded picture's strides, unpadded),
+   packed RGB and 4:2:2 / 4:4:4 layouts (its planes one after the other, rows tight) as a device picture, a tensor
+   file's frame as a device tensor; the device pads, converts, reduces or quantises it */
+static int gpu_push_source(void *ctx, const jm_device_source *src, const jmh_frame_params *fp, int n, const jmh_coded_slice *sl, int cw, int ch) {
+    const jm_pic *cur = src->pic;
+    const size_t ps = cur && cur->bd > 8 ? 2 : 1, luma = cur ? (size_t)cur->w * cur->h * ps : 0;
     int r;
-    if (!gpu_in.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_in.stream))) return r;
-    if (gpu_in.bytes < bytes) {
-        if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_in.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_in.buf))) return r;
-        gpu_in.bytes = bytes;
-    }
-    if ((r = jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, rgb, bytes, gpu_in.stream))) return r;
-    jmh_device_picture pic;
-    memset(&pic, 0, sizeof(pic));
-    pic.format = format;
-    pic.width = dw; pic.height = dh;
-    pic.plane[0] = gpu_in.buf;
-    pic.stride[0] = (int64_t)4 * dw;
-    pic.stream = gpu_in.stream;
-    return jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch);
-}
-/* DeviceInputYUV 32..37, 40..44: the 4:2:2 or 4:4:4 frame as read (its planes one after the other, rows tight),
-   through the same buffer and stream; the device reduces it to 4:2:0 */
-static int gpu_push_device_yuv(void *ctx, const void *frame, int format, int dw, int dh, const jmh_frame_params *fp, int n, const jmh_coded_slice *sl,
-                               int cw, int ch) {
-    const int layout = format & ~JMH_PIX_CHROMA_LEFT;
-    const size_t bytes = jm_yuv_frame_bytes(layout, dw, dh);
-    int r;
-    if (!gpu_in.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_in.stream))) return r;
-    if (gpu_in.bytes < bytes) {
-        if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_in.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_in.buf))) return r;
-        gpu_in.bytes = bytes;
-    }
-    if ((r = jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, frame, bytes, gpu_in.stream))) return r;
-    jmh_device_picture pic;
-    memset(&pic, 0, sizeof(pic));
-    pic.format = format;
-    pic.width = dw; pic.height = dh;
-    size_t off = 0;
-    for (int sp = 0; sp < 3 && jm_yuv_row_bytes(layout, sp, dw); sp++) {
-        pic.plane[sp] = (const uint8_t *)gpu_in.buf + off;
-        pic.stride[sp] = (int64_t)jm_yuv_row_bytes(layout, sp, dw);
-        off += jm_yuv_row_bytes(layout, sp, dw) * dh;
-    }
-    pic.stream = gpu_in.stream;
-    return jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch);
-}
-/* DeviceInputTensor 1..4: the frame as read (rgb24, gbrp, gbrp10le, gbrpf32le), through the same buffer and
-   stream, described as a device tensor; the device quantises and converts it */
-static int gpu_push_device_tensor(void *ctx, const void *frame, int kind, int flags, int dw, int dh, const jmh_frame_params *fp, int n,
-                                  const jmh_coded_slice *sl, int cw, int ch) {
-    const size_t bytes = jm_tensor_frame_bytes(kind, dw, dh), es = (size_t)jm_tensor_elem_bytes(kind), plane = es * dw * dh;
-    int r;
-    if (!gpu_in.stream && (r = jmh_device_stream_create((jmh_ctx *)ctx, &gpu_in.stream))) return r;
-    if (gpu_in.bytes < bytes) {
-        if ((r = jmh_device_free((jmh_ctx *)ctx, gpu_in.buf)) || (r = jmh_device_malloc((jmh_ctx *)ctx, bytes, &gpu_in.buf))) return r;
-        gpu_in.bytes = bytes;
-    }
-    if ((r = jmh_device_upload((jmh_ctx *)ctx, gpu_in.buf, frame, bytes, gpu_in.stream))) return r;
+    if ((r = cur ? gpu_in_upload(ctx, luma * 3 / 2, cur->bd > 8 ? (const void *)cur->Y : (const void *)cur->y)
+                 : gpu_in_upload(ctx, jm_source_frame_bytes(src), src->frame))) return r;
     const uint8_t *base = (const uint8_t *)gpu_in.buf;
-    jmh_device_tensor t;
-    memset(&t, 0, sizeof(t));
-    t.dtype = kind == 4 ? JMH_T_F32 : kind == 3 ? JMH_T_U16 : JMH_T_U8;
-    t.flags = flags;
-    t.width = dw; t.height = dh;
-    if (kind == 1) {   /* rgb24: pixels of R, G, B */
-        t.chan[0] = base; t.chan[1] = base + 1; t.chan[2] = base + 2;
-        t.stride_x = 3; t.stride_y = (int64_t)3 * dw;
-    } else {           /* gbrp*: planes G, B, R */
-        t.chan[0] = base + 2 * plane; t.chan[1] = base; t.chan[2] = base + plane;
-        t.stride_x = (int64_t)es; t.stride_y = (int64_t)es * dw;
+    if (src->kind == JM_SRC_TENSOR) {
+        const gpu_tensor_layout l = gpu_tensor_frame(src->code, src->w, src->h);
+        jmh_device_tensor t;
+        memset(&t, 0, sizeof(t));
+        t.dtype = l.dtype; t.flags = src->flags;
+        t.width = src->w; t.height = src->h;
+        for (int i = 0; i < 3; i++) t.chan[i] = base + l.off[i];
+        t.stride_x = l.stride_x; t.stride_y = l.stride_y;
+        t.stream = gpu_in.stream;
+        return jmh_frame_push_coded_tensor((jmh_ctx *)ctx, &t, fp, n, sl, cw, ch);
     }
-    t.stream = gpu_in.stream;
-    return jmh_frame_push_coded_tensor((jmh_ctx *)ctx, &t, fp, n, sl, cw, ch);
+    jmh_device_picture pic;
+    memset(&pic, 0, sizeof(pic));
+    pic.width = src->w; pic.height = src->h;
+    pic.stream = gpu_in.stream;
+    if (src->kind == JM_SRC_PLANES) {
+        pic.format = cur->bd > 8 ? JMH_PIX_I010 : JMH_PIX_I420;
+        pic.plane[0] = base; pic.plane[1] = base + luma; pic.plane[2] = base + luma + luma / 4;
+        pic.stride[0] = (int64_t)cur->w * ps; pic.stride[1] = pic.stride[2] = (int64_t)(cur->w / 2) * ps;
+        if (!n) return jmh_frame_push_device((jmh_ctx *)ctx, &pic, fp);
+    } else if (src->kind == JM_SRC_RGB) {
+        pic.format = src->code;
+        pic.plane[0] = base;
+        pic.stride[0] = (int64_t)4 * src->w;
+    } else {
+        const int layout = src->code & ~JMH_PIX_CHROMA_LEFT;
+        size_t off = 0;
+        pic.format = src->code;
+        for (int sp = 0; sp < 3 && jm_yuv_row_bytes(layout, sp, src->w); sp++) {
+            pic.plane[sp] = base + off;
+            pic.stride[sp] = (int64_t)jm_yuv_row_bytes(layout, sp, src->w);
+            off += jm_yuv_row_bytes(layout, sp, src->w) * src->h;
+        }
+    }
+    return jmh_frame_push_coded_device((jmh_ctx *)ctx, &pic, fp, n, sl, cw, ch);
 }
 /* DeviceReconFormat 16..19 / DeviceReconTensor 1..4: the current picture, deblocked, pulled at the display size into
    one device buffer in the file's layout, on a stream of the caller's, and downloaded behind it */
@@ -179,19 +147,13 @@ static int gpu_pull_recon(void *ctx, int format, int tensor, int flags, int dw, 
         pic.stream = gpu_out.stream;
         r = jmh_pull_picture((jmh_ctx *)ctx, JMH_OUT_DEBLOCKED, &pic);
     } else {
-        const size_t es = (size_t)jm_tensor_elem_bytes(tensor), plane = es * dw * dh;
+        const gpu_tensor_layout l = gpu_tensor_frame(tensor, dw, dh);
         jmh_device_tensor_out t;
         memset(&t, 0, sizeof(t));
-        t.dtype = tensor == 4 ? JMH_T_F32 : tensor == 3 ? JMH_T_U16 : JMH_T_U8;
-        t.flags = flags;
+        t.dtype = l.dtype; t.flags = flags;
         t.width = dw; t.height = dh;
-        if (tensor == 1) {   /* rgb24: pixels of R, G, B */
-            t.chan[0] = base; t.chan[1] = base + 1; t.chan[2] = base + 2;
-            t.stride_x = 3; t.stride_y = (int64_t)3 * dw;
-        } else {             /* gbrp*: planes G, B, R */
-            t.chan[0] = base + 2 * plane; t.chan[1] = base; t.chan[2] = base + plane;
-            t.stride_x = (int64_t)es; t.stride_y = (int64_t)es * dw;
-        }
+        for (int i = 0; i < 3; i++) t.chan[i] = base + l.off[i];
+        t.stride_x = l.stride_x; t.stride_y = l.stride_y;
         t.stream = gpu_out.stream;
         r = jmh_pull_tensor((jmh_ctx *)ctx, JMH_OUT_DEBLOCKED, &t);
     }
@@ -215,10 +177,7 @@ int main(int argc, char **argv) {
     jm_input inp;
     char err[1024];
     jm_input_defaults(&inp);
-    jm_set_device_input(gpu_push_device);   /* before PatchInp: it rejects DeviceInput on a backend without one */
-    jm_set_device_input_rgb(gpu_push_device_rgb);
-    jm_set_device_input_yuv(gpu_push_device_yuv);
-    jm_set_device_input_tensor(gpu_push_device_tensor);
+    jm_set_device_input(gpu_push_source);   /* before PatchInp: it rejects DeviceInput on a backend without one */
     jm_set_device_input_scale(gpu_input_scale);
     jm_set_device_output(gpu_pull_recon);
     if (jm_configure(&inp, argc, argv, err, sizeof(err))) { fprintf(stderr, "%s\n", err); return 1; }

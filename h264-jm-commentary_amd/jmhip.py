@@ -1130,42 +1130,57 @@ class Encoder:
         data = np.ascontiguousarray(data)
         _check(self.lib.jmh_device_upload(self.ctx, _addr(dst), _ptr(data), data.nbytes, stream), "jmh_device_upload")
 
-    def device_picture(self, layout, stream=None, base=None):
-        """A HostLayout (to_device, to_device_rgb, to_device_yuv) uploaded: into base, or into a new allocation of exactly its
-        bytes (the caller frees .base).  Returns the DevicePicture."""
+    # a device source is a DevicePicture or a DeviceTensor: its entry points end in "device" / "picture" or "tensor"
+    def _upload_layout(self, layout, stream, base):
         if base is None:
             base = self.device_alloc(layout.buf.nbytes)
         self.device_upload(base, layout.buf, stream)
-        pic = layout.at(base, stream)
-        pic.base = base
-        return pic
+        src = layout.at(base, stream)
+        src.base = base
+        return src
 
-    def push_device(self, pic, slice_type, qp, chroma_qp_offset=0, deblock=None):
-        """jmh_frame_push_device: push() of a DevicePicture; the library pads it to the coded size."""
+    def _push_src(self, src, slice_type, qp, chroma_qp_offset, deblock):
+        name = "jmh_frame_push_tensor" if isinstance(src, DeviceTensor) else "jmh_frame_push_device"
         fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
-        s = pic.struct()
-        _check(self.lib.jmh_frame_push_device(self.ctx, ctypes.byref(s), ctypes.byref(fp)), "jmh_frame_push_device")
+        s = src.struct()
+        _check(getattr(self.lib, name)(self.ctx, ctypes.byref(s), ctypes.byref(fp)), name)
 
-    def push_coded_device(self, pic, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0, heads=None):
-        """jmh_frame_push_coded_device: push_coded() of a DevicePicture."""
+    def _push_coded_src(self, src, slice_type, qp, descs, crop, deblock, chroma_qp_offset, heads):
+        name = "jmh_frame_push_coded_tensor" if isinstance(src, DeviceTensor) else "jmh_frame_push_coded_device"
         self._arm(heads)
         fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
         cw, ch = crop if crop is not None else (self.w, self.h)
         self._coded_n = getattr(self, "_coded_n", [])
-        s = pic.struct()
-        _check(self.lib.jmh_frame_push_coded_device(self.ctx, ctypes.byref(s), ctypes.byref(fp), len(descs), ctypes.cast(descs, _P), cw, ch),
-               "jmh_frame_push_coded_device")
+        s = src.struct()
+        _check(getattr(self.lib, name)(self.ctx, ctypes.byref(s), ctypes.byref(fp), len(descs), ctypes.cast(descs, _P), cw, ch), name)
         self._coded_n.append(len(descs))
+
+    def _ingest_src(self, src):
+        name = "jmh_ingest_tensor" if isinstance(src, DeviceTensor) else "jmh_ingest_picture"
+        y = np.empty((self.h, self.w), self.pdt)
+        u = np.empty((self.h // 2, self.w // 2), self.pdt)
+        v = np.empty_like(u)
+        s = src.struct()
+        _check(getattr(self.lib, name)(self.ctx, ctypes.byref(s), _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2), name)
+        return y, u, v
+
+    def device_picture(self, layout, stream=None, base=None):
+        """A HostLayout (to_device, to_device_rgb, to_device_yuv) uploaded: into base, or into a new allocation of exactly its
+        bytes (the caller frees .base).  Returns the DevicePicture."""
+        return self._upload_layout(layout, stream, base)
+
+    def push_device(self, pic, slice_type, qp, chroma_qp_offset=0, deblock=None):
+        """jmh_frame_push_device: push() of a DevicePicture; the library pads it to the coded size."""
+        self._push_src(pic, slice_type, qp, chroma_qp_offset, deblock)
+
+    def push_coded_device(self, pic, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0, heads=None):
+        """jmh_frame_push_coded_device: push_coded() of a DevicePicture."""
+        self._push_coded_src(pic, slice_type, qp, descs, crop, deblock, chroma_qp_offset, heads)
 
     def ingest(self, pic):
         """jmh_ingest_picture, the unit seam: the DevicePicture packed and padded by the kernel, as
         (y, u, v) of the coded size."""
-        y = np.empty((self.h, self.w), self.pdt)
-        u = np.empty((self.h // 2, self.w // 2), self.pdt)
-        v = np.empty_like(u)
-        s = pic.struct()
-        _check(self.lib.jmh_ingest_picture(self.ctx, ctypes.byref(s), _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2), "jmh_ingest_picture")
-        return y, u, v
+        return self._ingest_src(pic)
 
     # ---- device pushes scaled to a chosen size (include/jmhip_scale.h) ----
     def input_scale(self, out_w, out_h=None, filter=JMH_SCALE_LANCZOS3, chroma_left=False):
@@ -1191,12 +1206,7 @@ class Encoder:
     def device_tensor(self, layout, stream=None, base=None):
         """A TensorLayout (to_device_tensor) uploaded: into base, or into a new allocation of exactly
         its bytes (the caller frees .base).  Returns the DeviceTensor."""
-        if base is None:
-            base = self.device_alloc(layout.buf.nbytes)
-        self.device_upload(base, layout.buf, stream)
-        t = layout.at(base, stream)
-        t.base = base
-        return t
+        return self._upload_layout(layout, stream, base)
 
     def from_torch(self, t, layout=None, order="rgb", flags=0, stream=None):
         """The DeviceTensor of a torch tensor on this context's device, with no copy: addresses from
@@ -1236,30 +1246,16 @@ class Encoder:
 
     def push_tensor(self, t, slice_type, qp, chroma_qp_offset=0, deblock=None):
         """jmh_frame_push_tensor: push() of a DeviceTensor; the library quantises, converts and pads it."""
-        fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
-        s = t.struct()
-        _check(self.lib.jmh_frame_push_tensor(self.ctx, ctypes.byref(s), ctypes.byref(fp)), "jmh_frame_push_tensor")
+        self._push_src(t, slice_type, qp, chroma_qp_offset, deblock)
 
     def push_coded_tensor(self, t, slice_type, qp, descs, crop=None, deblock=None, chroma_qp_offset=0, heads=None):
         """jmh_frame_push_coded_tensor: push_coded() of a DeviceTensor."""
-        self._arm(heads)
-        fp = frame_params(slice_type, qp, chroma_qp_offset, deblock, self.cfg.rdo, self.cfg.bit_depth)
-        cw, ch = crop if crop is not None else (self.w, self.h)
-        self._coded_n = getattr(self, "_coded_n", [])
-        s = t.struct()
-        _check(self.lib.jmh_frame_push_coded_tensor(self.ctx, ctypes.byref(s), ctypes.byref(fp), len(descs), ctypes.cast(descs, _P), cw, ch),
-               "jmh_frame_push_coded_tensor")
-        self._coded_n.append(len(descs))
+        self._push_coded_src(t, slice_type, qp, descs, crop, deblock, chroma_qp_offset, heads)
 
     def ingest_tensor(self, t):
         """jmh_ingest_tensor, the unit seam: the DeviceTensor quantised, converted, packed and padded
         by the kernel, as (y, u, v) of the coded size."""
-        y = np.empty((self.h, self.w), self.pdt)
-        u = np.empty((self.h // 2, self.w // 2), self.pdt)
-        v = np.empty_like(u)
-        s = t.struct()
-        _check(self.lib.jmh_ingest_tensor(self.ctx, ctypes.byref(s), _ptr(y), _ptr(u), _ptr(v), self.w, self.w // 2), "jmh_ingest_tensor")
-        return y, u, v
+        return self._ingest_src(t)
 
     # ---- decoded pictures pulled on the device (include/jmhip_output.h) ----
     def pull(self, dst, which=JMH_OUT_DEBLOCKED):

@@ -370,6 +370,32 @@ def test_alternating_with_host_device_picture_and_rgb_pushes():
         ref.close()
 
 
+def test_seam_clamp_count_is_reset_by_seams_that_do_not_count():
+    """one 10-bit context of 16x16, seams of 16x16 sources in turn: an I010 picture with a known number of samples
+    above 1023 (the count), a u16 tensor (0), an RGB10A2 picture (0), the I010 picture again (the count again)"""
+    rng = np.random.default_rng(77)
+    planes = [rng.integers(0, 1024, s).astype(np.uint16) for s in ((16, 16), (8, 8), (8, 8))]
+    for pl, where, val in ((0, (3, 5), 1024), (0, (15, 15), 65535), (0, (0, 0), 4000), (1, (7, 0), 1024), (2, (2, 6), 2048)):
+        planes[pl][where] = val
+    over = sum(int((p > 1023).sum()) for p in planes)
+    assert over == 5
+    chans = [rng.integers(0, 1024, (16, 16)).astype(np.uint16) for _ in range(3)]
+    words = rng.integers(0, 1 << 32, (16, 16), dtype=np.uint64).astype(np.uint32)
+    enc = jmhip.Encoder(16, 16, search_range=8, bit_depth=10)
+    dev = []
+    try:
+        dev.append(enc.device_picture(jmhip.to_device(tuple(planes), jmhip.JMH_PIX_I010)))
+        dev.append(enc.device_tensor(layout_of(chans, U16, "chw")))
+        dev.append(enc.device_picture(jmhip.to_device_rgb(words, jmhip.JMH_PIX_RGB10A2)))
+        for src, want in ((dev[0], over), (dev[1], 0), (dev[2], 0), (dev[0], over)):
+            enc.ingest_tensor(src) if src is dev[1] else enc.ingest(src)
+            assert enc.input_clamped() == want
+    finally:
+        for d in dev:
+            enc.device_free(d.base)
+        enc.close()
+
+
 # ---- 8: a torch tensor --------------------------------------------------------------------------
 def test_torch_tensor_through_from_torch():
     """A float16 (3, H, W) torch tensor made by torch ops on a non-default torch stream, and its
